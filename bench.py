@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the K-hop propagation precompute (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config products]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config products] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the steps, writes its outputs if asked (--dump-outputs) and prints
+the JSON line with the headline figure.  --full adds everything measured or checked beside it (the
+objects listed below, which are null or absent on a plain line).
 
 One "step" = one full K-hop propagate ([X, ÂX, …, Â^K X]) of the configuration's synthetic
 power-law graph with inputs already resident in HBM: K = 10 hops of the
@@ -17,7 +21,15 @@ all_gather_into_tensor of the whole panel per hop.  Both are bitwise equal to 1 
 --gpus N without torchrun (WORLD_SIZE unset): this process spawns the N ranks itself (one worker
 process per GPU, 127.0.0.1 rendezvous) before touching any GPU, and forwards rank 0's line.
 
-Extra objects on the JSON line:
+--dump-outputs DIR: after the timed steps, what the last step left -- the arrays a caller of the timed
+path receives -- as DIR/<name>.npy in their own precision: hop_00 .. hop_KK (K-hop panels), last_hop or
+aggregate (the one-panel modes), scale_0 / scale_1 (wavelet); rank<r>_ in front on N > 1, every rank its
+own rows.  At most 64 MB in all: larger panels keep the same rows each, a sample drawn with a fixed seed
+(sample_rows.npy).  The graph and the features are seeded, so two runs with the same arguments write the
+same files.
+
+Extra objects on the JSON line with --full (a plain one-GPU K-hop line still has `roofline`, from the
+timed region and the committed counters, without the isolated launches):
   roofline         the SpMM hop (one hop = `launches_per_hop` column-block launches): HBM bytes
                    per hop from rocprofv3 PMC counters (2 * FETCH_SIZE + WRITE_SIZE, the gfx950
                    correction of MI355X_MICROARCH.md), measured by this run in separate --pmc
@@ -112,6 +124,13 @@ def parse():
                          "rank's share, else sampled rows against the oracle; sampled = always the latter")
     ap.add_argument("--parity-rows", type=int, default=2000,
                     help="one GPU: random rows (plus the 20 longest) checked against the oracle after timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the PMC passes, the one-shot call, the "
+                         "isolated roofline launches, the parity checks and the CPU baseline (--pmc, --roofline-reps, "
+                         "--parity-rows, --dist-parity, --cpu-seconds and --no-cpu-baseline act only with it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (at most "
+                         "64 MB in all: the same seeded sample of rows of every panel where they are larger)")
     ap.add_argument("--mode", default="auto", choices=["auto", "panels", "last"],
                     help="panels: all K+1 hop panels kept (GraphOp.propagate); last: two ping-pong "
                          "panels, only A^K X kept (SGC-style, fused aggregation); auto: panels if "
@@ -121,6 +140,29 @@ def parse():
 
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 48 * 2 ** 20      # --dump-outputs: well inside its 64 MB
+DUMP_SEED = 4321
+
+
+def dump_outputs(path, named, budget=DUMP_BUDGET_BYTES, prefix=""):
+    """--dump-outputs: the arrays the timed path left after its last step, as <path>/<prefix><name>.npy in
+    their own precision (fp32 / fp64).  named: [(name, [rows, columns] tensor)], all of the same row count.
+    Where they exceed `budget` bytes in all, every array keeps the same rows: a sample drawn with a
+    fixed seed (sorted), whose row numbers go to <prefix>sample_rows.npy (as fp64, exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    n_rows = int(named[0][1].shape[0])
+    per_row = sum(int(t.shape[1]) * t.element_size() for _, t in named) + 8
+    keep = min(n_rows, max(1, budget // per_row))
+    rows = np.arange(n_rows) if keep == n_rows else \
+        np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=keep, replace=False))
+    np.save(os.path.join(path, f"{prefix}sample_rows.npy"), rows.astype(np.float64))
+    idx = torch.from_numpy(rows).to(named[0][1].device)
+    for name, t in named:
+        assert t.dtype in (torch.float32, torch.float64) and int(t.shape[0]) == n_rows, name
+        np.save(os.path.join(path, f"{prefix}{name}.npy"), t[idx].cpu().numpy())
+    log(f"dumped {len(named)} array(s), {keep} of {n_rows} rows each, to {path}")
 
 
 def _cpu_model():
@@ -657,6 +699,27 @@ def run_wavelet(a, dev, world=1, rank=0, pmc=None):
         step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, [(f"scale_{s}", R[s]) for s in range(R.shape[0])])
+    res = {
+        "metric": "propagated edges/sec (wavelet-basis Chebyshev propagation)",
+        "value": a.steps * order * nnz / dt,
+        "unit": "propagated edges/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32",
+        "data": f"synthetic (R-MAT power-law graph with the {a.config} node/edge counts, U[-1,1) features)",
+        "config": {"workload": f"{a.config}-shaped heat-wavelet filter bank", "n_nodes": n, "nnz_L": nnz,
+                   "d": d, "chebyshev_order": order, "scales": [-0.5, 0.5], "lmax": lmax,
+                   "col_block": cb, "parallelism": "x1",
+                   "mode": ("fp32, one load-balanced launch per order with the Chebyshev epilogue fused"
+                            if fused else "fp32, split path (SpMM + epilogue launches)")
+                           + " (bit-identical to the fused Chebyshev kernel)"},
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+    if not a.full:
+        print(json.dumps(res), flush=True)
+        return
     # roofline: one order's launch at the block width (HIP events on the launch stream): a
     # Chebyshev step (srg_spmm_cheby_f32, T_{k+1} over T_{k-1}) with the fused epilogue, else the
     # SpMM launch of the split path
@@ -685,20 +748,8 @@ def run_wavelet(a, dev, world=1, rank=0, pmc=None):
     peak = roofline.MI355X_HBM_PEAK_GBS
     traffic = float(pmc["hbm_bytes_per_hop"]) if pmc is not None and int(pmc["launches_per_hop"]) == LB else None
     achieved = (traffic if traffic else b_comp) / kern_s / 1e9
-    res = {
-        "metric": "propagated edges/sec (wavelet-basis Chebyshev propagation)",
-        "value": a.steps * order * nnz / dt,
-        "unit": "propagated edges/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32",
-        "data": f"synthetic (R-MAT power-law graph with the {a.config} node/edge counts, U[-1,1) features)",
-        "config": {"workload": f"{a.config}-shaped heat-wavelet filter bank", "n_nodes": n, "nnz_L": nnz,
-                   "d": d, "chebyshev_order": order, "scales": [-0.5, 0.5], "lmax": lmax,
-                   "col_block": cb, "parallelism": "x1",
-                   "mode": ("fp32, one load-balanced launch per order with the Chebyshev epilogue fused"
-                            if fused else "fp32, split path (SpMM + epilogue launches)")
-                           + " (bit-identical to the fused Chebyshev kernel)"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
+    res["roofline"] = {
+                     "bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
                      "frac": achieved / peak, "traffic": traffic,
                      "achieved_basis": ("L2 -> fabric bytes per order's SpMM (Infinity-Cache hits included; PMC "
                                         "2 * FETCH_SIZE + WRITE_SIZE = traffic) / its time" if traffic
@@ -710,9 +761,7 @@ def run_wavelet(a, dev, world=1, rank=0, pmc=None):
                      "kernel_ms": kern_s * 1e3, "launches_per_hop": LB, "kernel_ms_per_launch": kern_s * 1e3 / LB,
                      "frac_no_reuse": b_alg / kern_s / 1e9 / peak, "frac_compulsory": b_comp / kern_s / 1e9 / peak,
                      "algorithmic_bytes_per_hop": b_alg, "compulsory_bytes_per_hop": b_comp,
-                     "traffic_over_compulsory": (traffic / b_comp) if traffic else None},
-        "cpu_baseline": None,
-    }
+                     "traffic_over_compulsory": (traffic / b_comp) if traffic else None}
     if not a.no_cpu_baseline:
         log("cpu baseline ...")
         host = (ip.cpu().numpy(), ix.cpu().numpy(), filt.fvals.cpu().numpy(), X.cpu().numpy())
@@ -766,10 +815,36 @@ def run_wavelet_f64(a, dev, pmc=None):
         step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # roofline: one Chebyshev STEP order (F T_k - T_{k-1}, both scales' R updated: every block launch and the
-    # hub workgroups, joined back), HIP events on the launch stream, over work panels of the block's width
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, [(f"scale_{s}", R[s]) for s in range(ns)])
     P64 = filt._plan64(cb)
     step_launches = P64.n_launch if P64 is not None else 1
+    res = {
+        "metric": "propagated edges/sec (wavelet-basis Chebyshev propagation)",
+        "value": a.steps * order * nnz / dt,
+        "unit": "propagated edges/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f64",
+        "data": f"synthetic (R-MAT power-law graph with the {a.config} node/edge counts, U[-1,1) features)",
+        "config": {"workload": f"{a.config}-shaped heat-wavelet filter bank, fp64 (the reference's precision)",
+                   "n_nodes": n, "nnz_L": nnz, "d": d, "col_block": cb,
+                   "columns_per_step": cb, "chebyshev_order": order, "scales": taus, "lmax": lmax,
+                   "parallelism": "x1",
+                   "mode": ("fp64, per order %d column-block launches of srg_plan_cheby_step_f64 + %d whole hub rows "
+                            "as hub workgroups beside them (SpMM + recurrence + both scales fused)"
+                            % (P64.col_blocks, P64.hub_rows_whole) if P64 is not None else
+                            "fp64, one srg_cheby_step_hub_f64 launch per order (SpMM + recurrence + both scales fused)")
+                           + ("" if cb == d else f"; a step filters one {cb}-column block of the {d}-column "
+                                                 "panel (the widest whose five fp64 panels fit)")},
+        "roofline": None,
+        "parity_vs_oracle": None,
+        "cpu_baseline": None,
+    }
+    if not a.full:
+        print(json.dumps(res), flush=True)
+        return
+    # roofline: one Chebyshev STEP order (F T_k - T_{k-1}, both scales' R updated: every block launch and the
+    # hub workgroups, joined back), HIP events on the launch stream, over work panels of the block's width
     from srgnn import _lib
     stream = torch.cuda.current_stream(dev)
     t_cur, t_old = torch.empty_like(S), torch.empty_like(S)
@@ -801,24 +876,8 @@ def run_wavelet_f64(a, dev, pmc=None):
               "checker": "oracle.cheby_op: oracle/srg_oracle.c's fp64 restatement of pygsp cheby_op (scipy's "
                          "csr_matvecs order), the whole graph"}
     log(f"parity vs oracle fp64: {parity['bit_exact']}")
-    res = {
-        "metric": "propagated edges/sec (wavelet-basis Chebyshev propagation)",
-        "value": a.steps * order * nnz / dt,
-        "unit": "propagated edges/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f64",
-        "data": f"synthetic (R-MAT power-law graph with the {a.config} node/edge counts, U[-1,1) features)",
-        "config": {"workload": f"{a.config}-shaped heat-wavelet filter bank, fp64 (the reference's precision)",
-                   "n_nodes": n, "nnz_L": nnz, "d": d, "col_block": cb,
-                   "columns_per_step": cb, "chebyshev_order": order, "scales": taus, "lmax": lmax,
-                   "parallelism": "x1",
-                   "mode": ("fp64, per order %d column-block launches of srg_plan_cheby_step_f64 + %d whole hub rows "
-                            "as hub workgroups beside them (SpMM + recurrence + both scales fused)"
-                            % (P64.col_blocks, P64.hub_rows_whole) if P64 is not None else
-                            "fp64, one srg_cheby_step_hub_f64 launch per order (SpMM + recurrence + both scales fused)")
-                           + ("" if cb == d else f"; a step filters one {cb}-column block of the {d}-column "
-                                                 "panel (the widest whose five fp64 panels fit)")},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
+    res["roofline"] = {
+                     "bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
                      "frac": achieved / peak, "traffic": traffic,
                      "achieved_basis": ("L2 -> fabric bytes of one Chebyshev STEP launch (PMC 2 * FETCH_SIZE + "
                                         "WRITE_SIZE = traffic) / its time" if traffic
@@ -831,10 +890,8 @@ def run_wavelet_f64(a, dev, pmc=None):
                      "kernel_ms": kern_s * 1e3, "launches_per_step": step_launches,
                      "frac_no_reuse": b_alg / kern_s / 1e9 / peak, "frac_compulsory": b_comp / kern_s / 1e9 / peak,
                      "algorithmic_bytes_per_launch": b_alg, "compulsory_bytes_per_launch": b_comp,
-                     "traffic_over_compulsory": (traffic / b_comp) if traffic else None},
-        "parity_vs_oracle": parity,
-        "cpu_baseline": None,
-    }
+                     "traffic_over_compulsory": (traffic / b_comp) if traffic else None}
+    res["parity_vs_oracle"] = parity
     if not a.no_cpu_baseline:
         log("cpu baseline ...")
         res["cpu_baseline"] = cpu_baseline_cheby64(host[0], host[1], filt.fvals.cpu().numpy(),
@@ -887,7 +944,7 @@ def run_wavelet_dist(a, dev, world, rank):
     # this rank's rows of the one-GPU filter bank on the whole graph, checked after the timed steps
     ref = None
     free, _ = torch.cuda.mem_get_info(dev)
-    if 6 * n * cb * esz < 0.5 * free:
+    if a.full and 6 * n * cb * esz < 0.5 * free:
         from srgnn import wavelet as W
         one = W.HeatWaveletFilter.from_device(ip, ix, lv, n, [-0.5, 0.5], order=order, lmax=lmax,
                                               dtype=tdt, heavy_threshold=a.heavy_threshold)
@@ -912,11 +969,15 @@ def run_wavelet_dist(a, dev, world, rank):
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if a.dump_outputs and R is not None:      # every rank its own rows, in its share of the budget
+        dump_outputs(a.dump_outputs, [(f"scale_{s}", R[s]) for s in range(R.shape[0])],
+                     budget=DUMP_BUDGET_BYTES // world, prefix=f"rank{rank}_")
     ok = ref is not None and R is not None and torch.equal(R, ref)
     flags = torch.tensor([int(ref is not None), int(ok)], dtype=torch.int32, device=dev)
     dist.all_reduce(flags, op=dist.ReduceOp.MIN)
     parity = ({"outputs_checked": "every scale, this rank's rows", "bitwise_equal_to_1gpu": bool(flags[1].item()),
-               "ranks": world} if flags[0].item() else {"skipped": "the whole graph's panels do not fit beside a rank's share"})
+               "ranks": world} if flags[0].item() else
+              {"skipped": "the whole graph's panels do not fit beside a rank's share" if a.full else "run with --full"})
     res = {"metric": "propagated edges/sec (wavelet-basis Chebyshev propagation)",
            "value": a.steps * order * nnz / dt, "unit": "propagated edges/s", "n_gpus": world,
            "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
@@ -946,7 +1007,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # the PMC passes are child processes: they must run before this process touches the GPU
     pmc = None
-    if world == 1 and not a.aggregate and not a.fused_epilogue and \
+    if a.full and world == 1 and not a.aggregate and not a.fused_epilogue and \
             (a.pmc == "on" or (a.pmc == "auto" and not _under_profiler())):
         pmc = measure_pmc(a)
     rank = int(os.environ.get("RANK", "0"))
@@ -989,7 +1050,7 @@ def main():
 
     stream = torch.cuda.current_stream(dev)
     mode = a.mode
-    ref_full = reference_hops(ip, ix, vals, n, X, K, dev) if world > 1 and a.dist_parity == "auto" else None
+    ref_full = reference_hops(ip, ix, vals, n, X, K, dev) if a.full and world > 1 and a.dist_parity == "auto" else None
     if world == 1:
         A = DeviceCSR.from_tensors(ip, ix, vals, n_cols=n, heavy_threshold=a.heavy_threshold, device=dev)
         if mode == "auto":
@@ -1064,20 +1125,20 @@ def main():
         local_rows, local_nnz = op.rows + op.n_ghost, op.nnz_local + int(op._ghost_pos.numel())
 
     one_shot_res = None
-    if world == 1 and mode == "panels" and K > 0 and not a.fast and \
+    if a.full and world == 1 and mode == "panels" and K > 0 and not a.fast and \
             torch.cuda.mem_get_info(dev)[0] > 1.3 * K * n * d * 4:
         one_shot(ip, ix, vals, n, X, K, dev, a.heavy_threshold)        # warm (allocator, code objects)
         one_shot_res = one_shot(ip, ix, vals, n, X, K, dev, a.heavy_threshold)
         log(f"one-shot propagate(K={K}): {one_shot_res['ms_total']:.1f} ms "
             f"({one_shot_res['ms_per_hop']:.2f} ms per hop)")
-    sample = oracle_sample(ip, ix, vals, n, a.parity_rows) if world == 1 and K > 0 else None
+    sample = oracle_sample(ip, ix, vals, n, a.parity_rows) if a.full and world == 1 and K > 0 else None
     refs = None
     if ref_full is not None:     # this rank's rows of the 1-GPU hops, checked after the timed steps
         refs = {k: v[op.r0:op.r1].clone() for k, v in ref_full.items()}
     del ref_full
     torch.cuda.empty_cache()
     host_copy = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         host_copy = (ip.cpu().numpy(), ix.cpu().numpy(), vals.cpu().numpy(), X.cpu().numpy())
     del ip, ix, vals
 
@@ -1121,6 +1182,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs:
+        # what a caller of the timed path receives: the K+1 hop panels, or the one panel the last-hop and
+        # aggregate modes return; N > 1: every rank its own rows, in its share of the budget
+        if mode == "panels" or world > 1:
+            named = [(f"hop_{k:02d}", p[: op.rows] if world > 1 else p) for k, p in enumerate(panels)]
+        else:
+            named = [("aggregate" if a.aggregate else "last_hop", panels[1])]
+        dump_outputs(a.dump_outputs, named, budget=DUMP_BUDGET_BYTES // world,
+                     prefix=f"rank{rank}_" if world > 1 else "")
 
     parity = None
     oracle_checks = None
@@ -1128,7 +1198,7 @@ def main():
         # hop 1 from X and hop K from hop K-1, as the timed steps left them
         oracle_checks = parity_vs_oracle(sample, [(1, panels[0], panels[1])] +
                                          ([(K, panels[K - 1], panels[K])] if K > 1 else []), tolerance=a.fast)
-    if world > 1:
+    if a.full and world > 1:
         # the N-GPU hops of this rank's rows against the 1-GPU kernels on the whole graph, bit for bit
         if a.fast:      # hub rows re-associated: normwise relative difference per row vs the exact hops
             ok = refs is not None and all(
@@ -1153,27 +1223,29 @@ def main():
 
     # roofline: average duration of one hop's SpMM launches on this rank (HIP events on the
     # launch stream; the hub side stream is joined back into it by the library)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * a.roofline_reps)]
-    if world == 1:
-        def one_hop():
-            hop(A, panels[0], panels[1], nt_store=a.nt_store, col_blocks=col_blocks, fast=a.fast)
-        if panels[1] is None:
-            panels[1] = torch.empty_like(X)
-    elif a.exchange == "allgather":
-        src = op._gather(panels[0])
+    kern_isolated_s = None
+    if a.full:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * a.roofline_reps)]
+        if world == 1:
+            def one_hop():
+                hop(A, panels[0], panels[1], nt_store=a.nt_store, col_blocks=col_blocks, fast=a.fast)
+            if panels[1] is None:
+                panels[1] = torch.empty_like(X)
+        elif a.exchange == "allgather":
+            src = op._gather(panels[0])
 
-        def one_hop():
-            spmm(A, src, out=panels[1][: op.rows])
-    else:
-        def one_hop():
-            op.compute(panels[0], panels[1])
-    for r in range(a.roofline_reps):
-        ev[2 * r].record(stream)
-        one_hop()
-        ev[2 * r + 1].record(stream)
-    torch.cuda.synchronize()
-    durs = [ev[2 * r].elapsed_time(ev[2 * r + 1]) * 1e-3 for r in range(a.roofline_reps)]
-    kern_isolated_s = float(np.mean(durs))
+            def one_hop():
+                spmm(A, src, out=panels[1][: op.rows])
+        else:
+            def one_hop():
+                op.compute(panels[0], panels[1])
+        for r in range(a.roofline_reps):
+            ev[2 * r].record(stream)
+            one_hop()
+            ev[2 * r + 1].record(stream)
+        torch.cuda.synchronize()
+        durs = [ev[2 * r].elapsed_time(ev[2 * r + 1]) * 1e-3 for r in range(a.roofline_reps)]
+        kern_isolated_s = float(np.mean(durs))
     if sample is not None and oracle_checks is None:
         # last-hop / aggregate modes keep no hop K-1: the isolated launches above left hop 1 of X
         # (the timed operator, the same launches) in panels[1]
@@ -1183,6 +1255,7 @@ def main():
     # few-microsecond gaps); on N GPUs the timed region also waits on the exchange, so the
     # isolated launches above are the kernel's duration there
     in_run = world == 1 and not a.aggregate and K > 0
+    # (a plain run has no isolated launches: its line has the roofline where the timed region gives the duration)
     kern_s = run_s / (a.steps * K) if in_run else kern_isolated_s
     b_alg = roofline.bytes_no_reuse(local_rows, local_nnz, d)
     b_comp = roofline.bytes_compulsory(local_rows, local_nnz, d, n_cols=n)
@@ -1195,7 +1268,7 @@ def main():
         if traffic and traffic_rd is not None else None
     # achieved: HBM bytes the counters saw per hop / hop time (a lower bound -- the compulsory
     # bytes -- where no counter run exists for this layout)
-    achieved = (traffic if traffic else b_comp) / kern_s / 1e9
+    achieved = (traffic if traffic else b_comp) / kern_s / 1e9 if kern_s is not None else None
 
     exchange_stats = {}
     if world > 1 and a.exchange == "halo":
@@ -1234,7 +1307,8 @@ def main():
                                if a.aggregate else "last hop only (2 ping-pong panels)")
                    if world == 1 else "all K+1 hop panels (row slices)",
                    **exchange_stats},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
+        "roofline": None if kern_s is None else
+                    {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
                      "frac": achieved / peak, "traffic": traffic,
                      "achieved_basis": ("L2 -> fabric bytes per hop (Infinity-Cache hits included; PMC "
                                         "2 * FETCH_SIZE + WRITE_SIZE = traffic) / hop time" if traffic else
@@ -1255,7 +1329,7 @@ def main():
                      "kernel_ms_per_launch": kern_s * 1e3 / launches,
                      "kernel_ms_source": ("HIP events over the timed steps / (steps x K)" if in_run
                                           else f"HIP events around {a.roofline_reps} isolated hop launches"),
-                     "kernel_ms_isolated": kern_isolated_s * 1e3,
+                     "kernel_ms_isolated": kern_isolated_s * 1e3 if a.full else None,
                      # SURVEY §8(d)'s no-reuse model counts every gathered X row as an HBM read, so
                      # cache hits push it past 1; the compulsory model counts every byte once
                      "frac_no_reuse": b_alg / kern_s / 1e9 / peak,

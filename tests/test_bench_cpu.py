@@ -23,6 +23,33 @@ def test_defaults(monkeypatch):
     a = b.parse()
     assert a.gpus == 1 and a.config == "products" and a.op == "khop" and a.exchange == "halo"
     assert a.steps >= 1 and a.warmup >= 0
+    assert a.full is False and a.dump_outputs is None      # a plain run: the headline figure only
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: panels inside the budget are written whole; larger ones keep the same seeded,
+    sorted sample of rows each (their numbers in sample_rows.npy), in the panels' own precision, inside
+    the budget, and the same rows on every call."""
+    import torch
+    b = _bench()
+    assert b.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+    n, d = 1000, 8
+    p32 = torch.arange(n * d, dtype=torch.float32).reshape(n, d)
+    p64 = -p32.to(torch.float64)
+    b.dump_outputs(str(tmp_path / "whole"), [("hop_00", p32), ("hop_01", p64)])
+    assert np.array_equal(np.load(tmp_path / "whole" / "hop_00.npy"), p32.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "sample_rows.npy"), np.arange(n, dtype=np.float64))
+    budget = 20000
+    for sub in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / sub), [("hop_00", p32), ("hop_01", p64)], budget=budget, prefix="rank1_")
+    rows = np.load(tmp_path / "s1" / "rank1_sample_rows.npy")
+    assert rows.dtype == np.float64 and 0 < rows.size < n and np.all(np.diff(rows) > 0)
+    r = rows.astype(np.int64)
+    a32, a64 = np.load(tmp_path / "s1" / "rank1_hop_00.npy"), np.load(tmp_path / "s1" / "rank1_hop_01.npy")
+    assert a32.dtype == np.float32 and a64.dtype == np.float64
+    assert np.array_equal(a32, p32.numpy()[r]) and np.array_equal(a64, p64.numpy()[r])
+    assert rows.nbytes + a32.nbytes + a64.nbytes <= budget
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "rank1_sample_rows.npy"))
 
 
 @pytest.mark.parametrize("force_port", [False, True])

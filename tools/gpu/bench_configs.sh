@@ -11,6 +11,6 @@ for spec in "$@"; do
     tag=$(echo "$cfg $extra" | tr -c 'A-Za-z0-9\n' '_' | sed 's/__*/_/g; s/_$//')
     i=$((i + 1))
     echo "== $cfg $extra" >&2
-    timeout -k 10 900 python "$R/bench.py" --config "$cfg" $extra > "$O/bench_${i}_$tag.json" 2> "$O/bench_${i}_$tag.err" || { echo "bench $cfg rc=$?" >&2; exit 1; }
+    timeout -k 10 900 python "$R/bench.py" --full --config "$cfg" $extra > "$O/bench_${i}_$tag.json" 2> "$O/bench_${i}_$tag.err" || { echo "bench $cfg rc=$?" >&2; exit 1; }
     cat "$O/bench_${i}_$tag.json"
 done
