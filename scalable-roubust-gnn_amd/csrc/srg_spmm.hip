@@ -1062,6 +1062,9 @@ k_spmm_hub(const IP* __restrict__ indptr, const int32_t* __restrict__ indices,
             if (qq == 0) av[nl] = a[b];
         }
     };
+    // an empty row (any schedule may name one a hub row): the consumer passes no barrier, so the
+    // producers, with nothing to gather, leave before their first
+    if (n_win == 0) return;
     // prologue: windows 0 and 1 in flight, window 0 published, window 2 in flight
     if (n_win > 0) {
         load_ids(0);
@@ -1084,7 +1087,7 @@ k_spmm_hub(const IP* __restrict__ indptr, const int32_t* __restrict__ indices,
         if (h + 4 < n_win) { gather(x0, a0); if (h + 5 < n_win) load_ids(h + 5); }
         __syncthreads();
     }
-    // barrier count: 1 (prologue) + (n_win - 1) in the loop == the consumer's n_win
+    // barrier count (n_win >= 1): 1 (prologue) + (n_win - 1) in the loop == the consumer's n_win
 }
 
 constexpr size_t kHubLdsBytes = HubGeom<kHubW>::LDS_BYTES;
@@ -1320,6 +1323,9 @@ k_cheby_hub64(const int64_t* __restrict__ indptr, const int32_t* __restrict__ in
             if (qq == 0) av[nl] = a[b];
         }
     };
+    // an empty row (any schedule may name one a hub row): the consumer passes no barrier, so the
+    // producers, with nothing to gather, leave before their first
+    if (n_win == 0) return;
     // prologue: windows 0 and 1 in flight, window 0 published, window 2 in flight
     if (n_win > 0) {
         load_ids(0);
@@ -1340,7 +1346,7 @@ k_cheby_hub64(const int64_t* __restrict__ indptr, const int32_t* __restrict__ in
         if (h + 4 < n_win) { gather(x0, a0); if (h + 5 < n_win) load_ids(h + 5); }
         __syncthreads();
     }
-    // barrier count: 1 (prologue) + (n_win - 1) in the loop == the consumer's n_win
+    // barrier count (n_win >= 1): 1 (prologue) + (n_win - 1) in the loop == the consumer's n_win
 }
 
 // the hub workgroups of n_items (row, slice) pairs on `s` (the window size by the launch's width)
