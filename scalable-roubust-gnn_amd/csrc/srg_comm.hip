@@ -23,7 +23,6 @@
 #include <dlfcn.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,22 +31,10 @@
 #include <vector>
 
 #include "srg_halo_internal.h"
+#include "srg_internal.h"
 #include "srgnn_hip.h"
 
-extern "C" void srg_set_error(int code, const char* msg);   // srg_spmm.hip: thread-local srg_last_error
-
 namespace {
-
-int comm_fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    srg_set_error(code, buf);
-    return code;
-}
 
 struct Rccl {
     void* handle = nullptr;
@@ -89,7 +76,7 @@ int load_rccl(const Rccl** out)
                 if (!h) h = dlopen(n, RTLD_NOW | RTLD_LOCAL);
             if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_LOCAL);
         }
-        if (!h) return comm_fail(SRG_ERR_HIP, "cannot load librccl: %s", dlerror());
+        if (!h) return srg_fail(SRG_ERR_HIP, "cannot load librccl: %s", dlerror());
         Rccl r;
         r.handle = h;
         if (!sym(h, "ncclGetUniqueId", r.GetUniqueId) || !sym(h, "ncclCommInitRank", r.CommInitRank) ||
@@ -97,7 +84,7 @@ int load_rccl(const Rccl** out)
             !sym(h, "ncclGroupStart", r.GroupStart) || !sym(h, "ncclGroupEnd", r.GroupEnd) ||
             !sym(h, "ncclSend", r.Send) || !sym(h, "ncclRecv", r.Recv) ||
             !sym(h, "ncclGetErrorString", r.GetErrorString))
-            return comm_fail(SRG_ERR_HIP, "librccl lacks an entry point: %s", dlerror());
+            return srg_fail(SRG_ERR_HIP, "librccl lacks an entry point: %s", dlerror());
         g_rccl = r;
     }
     *out = &g_rccl;
@@ -108,14 +95,7 @@ int load_rccl(const Rccl** out)
     do {                                                                                         \
         ncclResult_t e_ = (expr);                                                                \
         if (e_ != ncclSuccess)                                                                   \
-            return comm_fail(SRG_ERR_HIP, "%s failed: %s", #expr, (r)->GetErrorString(e_));      \
-    } while (0)
-
-#define SRG_HIPC(expr)                                                                           \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return comm_fail(SRG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
+            return srg_fail(SRG_ERR_HIP, "%s failed: %s", #expr, (r)->GetErrorString(e_));      \
     } while (0)
 
 struct DeviceScope {   // current device restored on exit
@@ -181,12 +161,12 @@ int dist_streams(srg_comm* comm)
     comm->peer_arrived.assign(L, std::vector<hipEvent_t>(comm->nranks, nullptr));
     comm->panel_ready.assign(L, nullptr);
     for (size_t i = 0; i < L; ++i) {
-        SRG_HIPC(hipSetDevice(comm->devices[i]));
-        SRG_HIPC(hipEventCreateWithFlags(&comm->panel_ready[i], hipEventDisableTiming));
+        SRG_HIP_CHECK(hipSetDevice(comm->devices[i]));
+        SRG_HIP_CHECK(hipEventCreateWithFlags(&comm->panel_ready[i], hipEventDisableTiming));
         for (int q = 0; q < comm->nranks; ++q) {
             if (q == comm->ranks[i]) continue;
-            SRG_HIPC(hipStreamCreateWithFlags(&comm->peer_stream[i][q], hipStreamNonBlocking));
-            SRG_HIPC(hipEventCreateWithFlags(&comm->peer_arrived[i][q], hipEventDisableTiming));
+            SRG_HIP_CHECK(hipStreamCreateWithFlags(&comm->peer_stream[i][q], hipStreamNonBlocking));
+            SRG_HIP_CHECK(hipEventCreateWithFlags(&comm->peer_arrived[i][q], hipEventDisableTiming));
         }
     }
     return SRG_OK;
@@ -213,8 +193,8 @@ int dist_exchange(const Rccl* r, srg_comm* comm, const srg_shard_f32* shards, in
                 const int i = local[side];
                 if (i < 0) continue;
                 const int peer = side ? a : b;
-                SRG_HIPC(hipSetDevice(shards[i].device));
-                SRG_HIPC(hipStreamWaitEvent(comm->peer_stream[i][peer], comm->panel_ready[i], 0));
+                SRG_HIP_CHECK(hipSetDevice(shards[i].device));
+                SRG_HIP_CHECK(hipStreamWaitEvent(comm->peer_stream[i][peer], comm->panel_ready[i], 0));
             }
             SRG_NCCL(r, r->GroupStart());
             int rc = SRG_OK;
@@ -231,18 +211,18 @@ int dist_exchange(const Rccl* r, srg_comm* comm, const srg_shard_f32* shards, in
                 if (n_me) e = r->Send(s.panels[k - 1], n_me, ncclFloat32, peer, comm->comms[i], ps);
                 if (e == ncclSuccess && n_peer)
                     e = r->Recv(s.x_full + (size_t)row_starts[peer] * ld, n_peer, ncclFloat32, peer, comm->comms[i], ps);
-                if (e != ncclSuccess) rc = comm_fail(SRG_ERR_HIP, "ncclSend / ncclRecv failed: %s", r->GetErrorString(e));
+                if (e != ncclSuccess) rc = srg_fail(SRG_ERR_HIP, "ncclSend / ncclRecv failed: %s", r->GetErrorString(e));
             }
             // every exit closes the group (RCCL's group state is thread-local and shared with torch)
             const ncclResult_t ge = r->GroupEnd();
             if (rc) return rc;
-            if (ge != ncclSuccess) return comm_fail(SRG_ERR_HIP, "ncclGroupEnd failed: %s", r->GetErrorString(ge));
+            if (ge != ncclSuccess) return srg_fail(SRG_ERR_HIP, "ncclGroupEnd failed: %s", r->GetErrorString(ge));
             for (int side = 0; side < 2; ++side) {
                 const int i = local[side];
                 if (i < 0) continue;
                 const int peer = side ? a : b;
-                SRG_HIPC(hipSetDevice(shards[i].device));
-                SRG_HIPC(hipEventRecord(comm->peer_arrived[i][peer], comm->peer_stream[i][peer]));
+                SRG_HIP_CHECK(hipSetDevice(shards[i].device));
+                SRG_HIP_CHECK(hipEventRecord(comm->peer_arrived[i][peer], comm->peer_stream[i][peer]));
             }
         }
     return SRG_OK;
@@ -254,7 +234,7 @@ extern "C" {
 
 int srg_comm_unique_id(void* id_out)
 {
-    if (!id_out) return comm_fail(SRG_ERR_INVALID, "null id buffer");
+    if (!id_out) return srg_fail(SRG_ERR_INVALID, "null id buffer");
     const Rccl* r = nullptr;
     int rc = load_rccl(&r);
     if (rc) return rc;
@@ -266,14 +246,14 @@ int srg_comm_unique_id(void* id_out)
 
 int srg_comm_init_rank(int nranks, const void* id, int rank, int device, srg_comm** out)
 {
-    if (!out || !id) return comm_fail(SRG_ERR_INVALID, "null argument");
+    if (!out || !id) return srg_fail(SRG_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (nranks < 1 || rank < 0 || rank >= nranks) return comm_fail(SRG_ERR_INVALID, "rank %d of %d", rank, nranks);
+    if (nranks < 1 || rank < 0 || rank >= nranks) return srg_fail(SRG_ERR_INVALID, "rank %d of %d", rank, nranks);
     const Rccl* r = nullptr;
     int rc = load_rccl(&r);
     if (rc) return rc;
     DeviceScope scope;
-    SRG_HIPC(hipSetDevice(device));
+    SRG_HIP_CHECK(hipSetDevice(device));
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof(uid));
     ncclComm_t c = nullptr;
@@ -281,7 +261,7 @@ int srg_comm_init_rank(int nranks, const void* id, int rank, int device, srg_com
     srg_comm* comm = new (std::nothrow) srg_comm();
     if (!comm) {
         (void)r->CommDestroy(c);
-        return comm_fail(SRG_ERR_ALLOC, "out of host memory");
+        return srg_fail(SRG_ERR_ALLOC, "out of host memory");
     }
     comm->nranks = nranks;
     comm->comms = {c};
@@ -293,9 +273,9 @@ int srg_comm_init_rank(int nranks, const void* id, int rank, int device, srg_com
 
 int srg_comm_init_all(int ndev, const int* devices, srg_comm** out)
 {
-    if (!out) return comm_fail(SRG_ERR_INVALID, "null argument");
+    if (!out) return srg_fail(SRG_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (ndev < 1) return comm_fail(SRG_ERR_INVALID, "ndev=%d < 1", ndev);
+    if (ndev < 1) return srg_fail(SRG_ERR_INVALID, "ndev=%d < 1", ndev);
     const Rccl* r = nullptr;
     int rc = load_rccl(&r);
     if (rc) return rc;
@@ -307,7 +287,7 @@ int srg_comm_init_all(int ndev, const int* devices, srg_comm** out)
     srg_comm* comm = new (std::nothrow) srg_comm();
     if (!comm) {
         for (auto c : cs) (void)r->CommDestroy(c);
-        return comm_fail(SRG_ERR_ALLOC, "out of host memory");
+        return srg_fail(SRG_ERR_ALLOC, "out of host memory");
     }
     comm->nranks = ndev;
     comm->comms = cs;
@@ -319,13 +299,13 @@ int srg_comm_init_all(int ndev, const int* devices, srg_comm** out)
 
 int srg_comm_init_loopback(int nranks, int device, srg_comm** out)
 {
-    if (!out) return comm_fail(SRG_ERR_INVALID, "null argument");
+    if (!out) return srg_fail(SRG_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (nranks < 1) return comm_fail(SRG_ERR_INVALID, "nranks=%d < 1", nranks);
+    if (nranks < 1) return srg_fail(SRG_ERR_INVALID, "nranks=%d < 1", nranks);
     DeviceScope scope;
-    SRG_HIPC(hipSetDevice(device));
+    SRG_HIP_CHECK(hipSetDevice(device));
     srg_comm* comm = new (std::nothrow) srg_comm();
-    if (!comm) return comm_fail(SRG_ERR_ALLOC, "out of host memory");
+    if (!comm) return srg_fail(SRG_ERR_ALLOC, "out of host memory");
     comm->nranks = nranks;
     comm->loopback = true;
     for (int i = 0; i < nranks; ++i) {
@@ -335,7 +315,7 @@ int srg_comm_init_loopback(int nranks, int device, srg_comm** out)
     if (hipStreamCreateWithFlags(&comm->lb_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&comm->lb_done, hipEventDisableTiming) != hipSuccess) {
         srg_comm_destroy(comm);
-        return comm_fail(SRG_ERR_HIP, "loopback stream / event creation failed");
+        return srg_fail(SRG_ERR_HIP, "loopback stream / event creation failed");
     }
     *out = comm;
     return SRG_OK;
@@ -376,7 +356,7 @@ int srg_comm_destroy(srg_comm* comm)
     for (auto c : comm->comms) {
         ncclResult_t e = r->CommDestroy(c);
         if (e != ncclSuccess && first == SRG_OK)
-            first = comm_fail(SRG_ERR_HIP, "ncclCommDestroy failed: %s", r->GetErrorString(e));
+            first = srg_fail(SRG_ERR_HIP, "ncclCommDestroy failed: %s", r->GetErrorString(e));
     }
     delete comm;
     return first;
@@ -387,26 +367,26 @@ int srg_comm_size(const srg_comm* comm) { return comm ? comm->nranks : 0; }
 int srg_dist_propagate_khop_f32(srg_comm* comm, const srg_shard_f32* shards, int n_shards,
                                 const int64_t* row_starts, int64_t ld, int32_t d, int32_t K)
 {
-    if (!comm || !shards || !row_starts) return comm_fail(SRG_ERR_INVALID, "null argument");
-    if (comm->loopback) return comm_fail(SRG_ERR_INVALID, "a loopback communicator serves srg_halo_propagate_f32 only");
+    if (!comm || !shards || !row_starts) return srg_fail(SRG_ERR_INVALID, "null argument");
+    if (comm->loopback) return srg_fail(SRG_ERR_INVALID, "a loopback communicator serves srg_halo_propagate_f32 only");
     if (n_shards != (int)comm->comms.size())
-        return comm_fail(SRG_ERR_INVALID, "%d shards for %d local ranks", n_shards, (int)comm->comms.size());
-    if (K < 0 || d < 0 || ld < d) return comm_fail(SRG_ERR_INVALID, "K=%d d=%d ld=%lld", K, d, (long long)ld);
+        return srg_fail(SRG_ERR_INVALID, "%d shards for %d local ranks", n_shards, (int)comm->comms.size());
+    if (K < 0 || d < 0 || ld < d) return srg_fail(SRG_ERR_INVALID, "K=%d d=%d ld=%lld", K, d, (long long)ld);
     const int P = comm->nranks;
     for (int q = 0; q < P; ++q)
         if (row_starts[q + 1] < row_starts[q] || row_starts[0] != 0)
-            return comm_fail(SRG_ERR_INVALID, "row_starts must start at 0 and be non-decreasing");
+            return srg_fail(SRG_ERR_INVALID, "row_starts must start at 0 and be non-decreasing");
     for (int i = 0; i < n_shards; ++i) {
         const srg_shard_f32& s = shards[i];
         const int r = comm->ranks[i];
         if (s.row0 != row_starts[r] || s.n_rows != row_starts[r + 1] - row_starts[r])
-            return comm_fail(SRG_ERR_INVALID, "shard %d (rank %d) rows [%lld, +%lld) != row_starts block",
-                             i, r, (long long)s.row0, (long long)s.n_rows);
+            return srg_fail(SRG_ERR_INVALID, "shard %d (rank %d) rows [%lld, +%lld) != row_starts block",
+                            i, r, (long long)s.row0, (long long)s.n_rows);
         if (s.device != comm->devices[i])
-            return comm_fail(SRG_ERR_INVALID, "shard %d on device %d, its communicator on %d", i, s.device,
-                             comm->devices[i]);
-        if (!s.x_full || !s.panels) return comm_fail(SRG_ERR_INVALID, "shard %d: null buffers", i);
-        if (s.n_rows > 0 && !s.indptr) return comm_fail(SRG_ERR_INVALID, "shard %d: null indptr", i);
+            return srg_fail(SRG_ERR_INVALID, "shard %d on device %d, its communicator on %d", i, s.device,
+                            comm->devices[i]);
+        if (!s.x_full || !s.panels) return srg_fail(SRG_ERR_INVALID, "shard %d: null buffers", i);
+        if (s.n_rows > 0 && !s.indptr) return srg_fail(SRG_ERR_INVALID, "shard %d: null indptr", i);
     }
     if (K == 0 || d == 0) return SRG_OK;
     const Rccl* r = nullptr;
@@ -434,12 +414,12 @@ int srg_dist_propagate_khop_f32(srg_comm* comm, const srg_shard_f32* shards, int
     };
     for (int i = 0; i < n_shards; ++i) {
         const srg_shard_f32& s = shards[i];
-        SRG_HIPC(hipSetDevice(s.device));
+        SRG_HIP_CHECK(hipSetDevice(s.device));
         // [P + 1] bounds, [P - 1][n_rows] split points, one status word
         const size_t bytes = (size_t)(P + 1) * 8 + (size_t)(P - 1) * (size_t)s.n_rows * 8 + 8;
         if (hipMallocAsync(reinterpret_cast<void**>(&splits[i]), bytes, st(i)) != hipSuccess) {
             release();
-            return comm_fail(SRG_ERR_HIP, "shard %d: hipMallocAsync of %zu bytes failed", i, bytes);
+            return srg_fail(SRG_ERR_HIP, "shard %d: hipMallocAsync of %zu bytes failed", i, bytes);
         }
         int64_t* bounds = splits[i] + (size_t)(P - 1) * s.n_rows;
         bad = reinterpret_cast<int*>(bounds + P + 1);
@@ -456,11 +436,11 @@ int srg_dist_propagate_khop_f32(srg_comm* comm, const srg_shard_f32* shards, int
         if (e == hipSuccess) e = hipStreamSynchronize(st(i));
         if (e != hipSuccess) {
             release();
-            return comm_fail(SRG_ERR_HIP, "shard %d: owner splits failed: %s", i, hipGetErrorString(e));
+            return srg_fail(SRG_ERR_HIP, "shard %d: owner splits failed: %s", i, hipGetErrorString(e));
         }
         if (flag) {
             release();
-            return comm_fail(SRG_ERR_INVALID, "shard %d: a row's column ids are not sorted (the owner-chunked exchange "
+            return srg_fail(SRG_ERR_INVALID, "shard %d: a row's column ids are not sorted (the owner-chunked exchange "
                                               "needs Â's canonical rows, SSRG/operators/utils.py:81-93)", i);
         }
     }
@@ -468,12 +448,12 @@ int srg_dist_propagate_khop_f32(srg_comm* comm, const srg_shard_f32* shards, int
         for (int i = 0; i < n_shards && !rc; ++i) {
             const srg_shard_f32& s = shards[i];
             if (hipSetDevice(s.device) != hipSuccess || hipEventRecord(comm->panel_ready[i], st(i)) != hipSuccess)
-                rc = comm_fail(SRG_ERR_HIP, "shard %d: panel event failed", i);
+                rc = srg_fail(SRG_ERR_HIP, "shard %d: panel event failed", i);
             // the own block is in place at once; the peers' blocks arrive on the pair streams
             else if (s.n_rows && hipMemcpyAsync(s.x_full + (size_t)s.row0 * ld, s.panels[k - 1],
                                                 (size_t)s.n_rows * ld * sizeof(float), hipMemcpyDeviceToDevice,
                                                 st(i)) != hipSuccess)
-                rc = comm_fail(SRG_ERR_HIP, "shard %d: own block copy failed", i);
+                rc = srg_fail(SRG_ERR_HIP, "shard %d: own block copy failed", i);
         }
         if (!rc) rc = dist_exchange(r, comm, shards, n_shards, row_starts, ld, k);
         // block q of every row once rank q's rows are in x_full, ascending q: the chains in CSR order
@@ -481,12 +461,12 @@ int srg_dist_propagate_khop_f32(srg_comm* comm, const srg_shard_f32* shards, int
             const srg_shard_f32& s = shards[i];
             const int me = comm->ranks[i];
             if (hipSetDevice(s.device) != hipSuccess) {
-                rc = comm_fail(SRG_ERR_HIP, "hipSetDevice(%d) failed", s.device);
+                rc = srg_fail(SRG_ERR_HIP, "hipSetDevice(%d) failed", s.device);
                 break;
             }
             for (int q = 0; q < P && !rc; ++q) {
                 if (q != me && hipStreamWaitEvent(st(i), comm->peer_arrived[i][q], 0) != hipSuccess) {
-                    rc = comm_fail(SRG_ERR_HIP, "shard %d: wait for rank %d failed", i, q);
+                    rc = srg_fail(SRG_ERR_HIP, "shard %d: wait for rank %d failed", i, q);
                     break;
                 }
                 if (s.n_rows == 0) continue;
@@ -540,7 +520,7 @@ int halo_pack(srg_halo_share* S, int g, const float* panel, int32_t d, hipStream
                                      d, d, s);
         if (rc) return rc;
     }
-    SRG_HIPC(hipEventRecord(S->packed[g], s));
+    SRG_HIP_CHECK(hipEventRecord(S->packed[g], s));
     return SRG_OK;
 }
 
@@ -552,7 +532,7 @@ int halo_transport(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares,
     const int P = comm->nranks;
     if (comm->loopback) {
         hipStream_t L = comm->lb_stream;
-        for (int i = 0; i < n; ++i) SRG_HIPC(hipStreamWaitEvent(L, shares[i]->packed[g], 0));
+        for (int i = 0; i < n; ++i) SRG_HIP_CHECK(hipStreamWaitEvent(L, shares[i]->packed[g], 0));
         for (int q = 0; q < n; ++q) {
             const srg_halo_plan& pq = *shares[q]->plan;
             int64_t roff = recv_base(pq, g);
@@ -564,7 +544,7 @@ int halo_transport(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares,
                     int64_t soff = shares[s]->send_off[g];
                     for (int t = 0; t < q; ++t)
                         if (t != s) soff += send_count(ps, g, t);
-                    SRG_HIPC(hipMemcpyAsync(dst[q] + roff * d, shares[s]->sendbuf + soff * d,
+                    SRG_HIP_CHECK(hipMemcpyAsync(dst[q] + roff * d, shares[s]->sendbuf + soff * d,
                                             (size_t)cnt * d * sizeof(float), hipMemcpyDeviceToDevice, L));
                 }
                 roff += cnt;
@@ -573,8 +553,8 @@ int halo_transport(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares,
         return SRG_OK;
     }
     for (int i = 0; i < n; ++i) {
-        SRG_HIPC(hipSetDevice(shares[i]->device));
-        SRG_HIPC(hipStreamWaitEvent(shares[i]->comm_stream, shares[i]->packed[g], 0));
+        SRG_HIP_CHECK(hipSetDevice(shares[i]->device));
+        SRG_HIP_CHECK(hipStreamWaitEvent(shares[i]->comm_stream, shares[i]->packed[g], 0));
     }
     SRG_NCCL(r, r->GroupStart());
     int rc = SRG_OK;
@@ -590,7 +570,7 @@ int halo_transport(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares,
             if (sc > 0) e = r->Send(S->sendbuf + soff * d, (size_t)sc * d, ncclFloat32, q, comm->comms[i], S->comm_stream);
             if (e == ncclSuccess && rcn > 0)
                 e = r->Recv(dst[i] + roff * d, (size_t)rcn * d, ncclFloat32, q, comm->comms[i], S->comm_stream);
-            if (e != ncclSuccess) rc = comm_fail(SRG_ERR_HIP, "ncclSend / ncclRecv failed: %s", r->GetErrorString(e));
+            if (e != ncclSuccess) rc = srg_fail(SRG_ERR_HIP, "ncclSend / ncclRecv failed: %s", r->GetErrorString(e));
             soff += sc;
             roff += rcn;
         }
@@ -598,7 +578,7 @@ int halo_transport(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares,
     // every exit closes the group (RCCL's group state is thread-local and shared with torch)
     const ncclResult_t ge = r->GroupEnd();
     if (rc) return rc;
-    if (ge != ncclSuccess) return comm_fail(SRG_ERR_HIP, "ncclGroupEnd failed: %s", r->GetErrorString(ge));
+    if (ge != ncclSuccess) return srg_fail(SRG_ERR_HIP, "ncclGroupEnd failed: %s", r->GetErrorString(ge));
     return SRG_OK;
 }
 
@@ -621,8 +601,8 @@ int exchange_words(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares,
     for (int i = 0; i < n; ++i)
         if (hipSetDevice(shares[i]->device) != hipSuccess ||
             hipMemcpy(buf[i], mine[i].data(), (size_t)P * len * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
-            return comm_fail(SRG_ERR_HIP, "share %d: count upload failed", i);
-    if (r->GroupStart() != ncclSuccess) return comm_fail(SRG_ERR_HIP, "ncclGroupStart failed");
+            return srg_fail(SRG_ERR_HIP, "share %d: count upload failed", i);
+    if (r->GroupStart() != ncclSuccess) return srg_fail(SRG_ERR_HIP, "ncclGroupStart failed");
     int rc = SRG_OK;
     for (int i = 0; i < n && !rc; ++i) {
         const int me = comm->ranks[i];
@@ -631,17 +611,17 @@ int exchange_words(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares,
             ncclResult_t e = r->Send(buf[i] + (size_t)q * len, len, ncclInt64, q, comm->comms[i], shares[i]->comm_stream);
             if (e == ncclSuccess)
                 e = r->Recv(buf[i] + (size_t)(P + q) * len, len, ncclInt64, q, comm->comms[i], shares[i]->comm_stream);
-            if (e != ncclSuccess) rc = comm_fail(SRG_ERR_HIP, "count exchange failed: %s", r->GetErrorString(e));
+            if (e != ncclSuccess) rc = srg_fail(SRG_ERR_HIP, "count exchange failed: %s", r->GetErrorString(e));
         }
     }
     const ncclResult_t ge = r->GroupEnd();
-    if (!rc && ge != ncclSuccess) rc = comm_fail(SRG_ERR_HIP, "count exchange: ncclGroupEnd failed: %s", r->GetErrorString(ge));
+    if (!rc && ge != ncclSuccess) rc = srg_fail(SRG_ERR_HIP, "count exchange: ncclGroupEnd failed: %s", r->GetErrorString(ge));
     theirs.assign(n, std::vector<int64_t>((size_t)P * len, 0));
     for (int i = 0; i < n && !rc; ++i)
         if (hipSetDevice(shares[i]->device) != hipSuccess || hipStreamSynchronize(shares[i]->comm_stream) != hipSuccess ||
             hipMemcpy(theirs[i].data(), buf[i] + (size_t)P * len, (size_t)P * len * sizeof(int64_t), hipMemcpyDeviceToHost) !=
                 hipSuccess)
-            rc = comm_fail(SRG_ERR_HIP, "share %d: count exchange readback failed", i);
+            rc = srg_fail(SRG_ERR_HIP, "share %d: count exchange readback failed", i);
     return rc;
 }
 
@@ -666,7 +646,7 @@ int verify_counts(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares, 
         if (hipSetDevice(shares[i]->device) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&buf[i]), (size_t)2 * P * NG * sizeof(int64_t)) != hipSuccess) {
             release();
-            return comm_fail(SRG_ERR_HIP, "share %d: count buffers failed", i);
+            return srg_fail(SRG_ERR_HIP, "share %d: count buffers failed", i);
         }
     // 1: the header, kCountHeader words per peer whatever the plan
     std::vector<std::vector<int64_t>> mine(n), theirs;
@@ -688,13 +668,13 @@ int verify_counts(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares, 
             if (q == comm->ranks[i]) continue;
             const int64_t* t = theirs[i].data() + (size_t)q * kCountHeader;
             if (t[1] != pl.n || t[2] != pl.nnz_total)
-                rc = comm_fail(SRG_ERR_INVALID, "rank %d's plan is of a graph with n=%lld nnz=%lld, rank %d's of n=%lld "
-                               "nnz=%lld", q, (long long)t[1], (long long)t[2], comm->ranks[i], (long long)pl.n,
-                               (long long)pl.nnz_total);
+                rc = srg_fail(SRG_ERR_INVALID, "rank %d's plan is of a graph with n=%lld nnz=%lld, rank %d's of n=%lld "
+                              "nnz=%lld", q, (long long)t[1], (long long)t[2], comm->ranks[i], (long long)pl.n,
+                              (long long)pl.nnz_total);
             else if (t[0] != pl.C || t[3] != P)
-                rc = comm_fail(SRG_ERR_INVALID, "plans disagree: rank %d's plan has %lld row chunks over %lld ranks, rank "
-                               "%d's %d over %d (build every rank's plan with the same arguments)", q, (long long)t[0],
-                               (long long)t[3], comm->ranks[i], pl.C, P);
+                rc = srg_fail(SRG_ERR_INVALID, "plans disagree: rank %d's plan has %lld row chunks over %lld ranks, rank "
+                              "%d's %d over %d (build every rank's plan with the same arguments)", q, (long long)t[0],
+                              (long long)t[3], comm->ranks[i], pl.C, P);
         }
     }
     // 2: the per-group counts (every plan has the same C now)
@@ -714,9 +694,9 @@ int verify_counts(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares, 
                 const int64_t* t = theirs[i].data() + (size_t)q * len;
                 for (int g = 0; g <= C + 1 && !rc; ++g)
                     if (t[g] != recv_count(pl, g, q))
-                        rc = comm_fail(SRG_ERR_INVALID, "plans disagree: rank %d sends %lld rows of group %d to rank %d, "
-                                       "which expects %lld (build every rank's plan with the same arguments)", q,
-                                       (long long)t[g], g, comm->ranks[i], (long long)recv_count(pl, g, q));
+                        rc = srg_fail(SRG_ERR_INVALID, "plans disagree: rank %d sends %lld rows of group %d to rank %d, "
+                                      "which expects %lld (build every rank's plan with the same arguments)", q,
+                                      (long long)t[g], g, comm->ranks[i], (long long)recv_count(pl, g, q));
             }
         }
     }
@@ -730,15 +710,15 @@ int verify_counts(const Rccl* r, srg_comm* comm, srg_halo_share* const* shares, 
 int halo_finish(srg_comm* comm, srg_halo_share* const* shares, int n, void* const* streams)
 {
     if (comm->loopback) {
-        SRG_HIPC(hipEventRecord(comm->lb_done, comm->lb_stream));
+        SRG_HIP_CHECK(hipEventRecord(comm->lb_done, comm->lb_stream));
         for (int i = 0; i < n; ++i)
-            SRG_HIPC(hipStreamWaitEvent(streams ? static_cast<hipStream_t>(streams[i]) : nullptr, comm->lb_done, 0));
+            SRG_HIP_CHECK(hipStreamWaitEvent(streams ? static_cast<hipStream_t>(streams[i]) : nullptr, comm->lb_done, 0));
         return SRG_OK;
     }
     for (int i = 0; i < n; ++i) {
-        SRG_HIPC(hipSetDevice(shares[i]->device));
-        SRG_HIPC(hipEventRecord(shares[i]->comm_done, shares[i]->comm_stream));
-        SRG_HIPC(hipStreamWaitEvent(streams ? static_cast<hipStream_t>(streams[i]) : nullptr, shares[i]->comm_done, 0));
+        SRG_HIP_CHECK(hipSetDevice(shares[i]->device));
+        SRG_HIP_CHECK(hipEventRecord(shares[i]->comm_done, shares[i]->comm_stream));
+        SRG_HIP_CHECK(hipStreamWaitEvent(streams ? static_cast<hipStream_t>(streams[i]) : nullptr, shares[i]->comm_done, 0));
     }
     return SRG_OK;
 }
@@ -750,37 +730,37 @@ extern "C" {
 int srg_halo_propagate_f32(srg_comm* comm, srg_halo_share* const* shares, int n_shards, float* const* const* panels,
                            int64_t ld, int32_t d, int32_t K, uint32_t flags, void* const* streams)
 {
-    if (!comm || !shares || !panels) return comm_fail(SRG_ERR_INVALID, "null argument");
+    if (!comm || !shares || !panels) return srg_fail(SRG_ERR_INVALID, "null argument");
     const int P = comm->nranks;
     const int local = comm->loopback ? P : (int)comm->comms.size();
-    if (n_shards != local) return comm_fail(SRG_ERR_INVALID, "%d shares for %d local ranks", n_shards, local);
-    if (K < 0 || d < 0) return comm_fail(SRG_ERR_INVALID, "K=%d d=%d", K, d);
-    if (ld != d) return comm_fail(SRG_ERR_INVALID, "ld=%lld != d=%d: the halo rows are contiguous exchange buffers",
-                                  (long long)ld, d);
+    if (n_shards != local) return srg_fail(SRG_ERR_INVALID, "%d shares for %d local ranks", n_shards, local);
+    if (K < 0 || d < 0) return srg_fail(SRG_ERR_INVALID, "K=%d d=%d", K, d);
+    if (ld != d) return srg_fail(SRG_ERR_INVALID, "ld=%lld != d=%d: the halo rows are contiguous exchange buffers",
+                                 (long long)ld, d);
     int C = -1;
     for (int i = 0; i < n_shards; ++i) {
         const srg_halo_share* S = shares[i];
-        if (!S || !S->plan || !panels[i]) return comm_fail(SRG_ERR_INVALID, "share %d: null share or panels", i);
+        if (!S || !S->plan || !panels[i]) return srg_fail(SRG_ERR_INVALID, "share %d: null share or panels", i);
         const srg_halo_plan& pl = *S->plan;
         if (pl.P != P || pl.p != comm->ranks[i])
-            return comm_fail(SRG_ERR_INVALID, "share %d is rank %d of %d, its communicator rank %d of %d", i, pl.p, pl.P,
-                             comm->ranks[i], P);
+            return srg_fail(SRG_ERR_INVALID, "share %d is rank %d of %d, its communicator rank %d of %d", i, pl.p, pl.P,
+                            comm->ranks[i], P);
         if (S->device != comm->devices[i])
-            return comm_fail(SRG_ERR_INVALID, "share %d on device %d, its communicator on %d", i, S->device, comm->devices[i]);
-        if (d > S->d_cap) return comm_fail(SRG_ERR_INVALID, "d=%d > the share's d_max=%lld", d, (long long)S->d_cap);
-        if (C >= 0 && pl.C != C) return comm_fail(SRG_ERR_INVALID, "shares with different chunk counts");
+            return srg_fail(SRG_ERR_INVALID, "share %d on device %d, its communicator on %d", i, S->device, comm->devices[i]);
+        if (d > S->d_cap) return srg_fail(SRG_ERR_INVALID, "d=%d > the share's d_max=%lld", d, (long long)S->d_cap);
+        if (C >= 0 && pl.C != C) return srg_fail(SRG_ERR_INVALID, "shares with different chunk counts");
         C = pl.C;
         for (int k = 0; k <= K; ++k)
-            if (!panels[i][k] && d > 0) return comm_fail(SRG_ERR_INVALID, "share %d: panels[%d] is null", i, k);
+            if (!panels[i][k] && d > 0) return srg_fail(SRG_ERR_INVALID, "share %d: panels[%d] is null", i, k);
     }
     if (comm->loopback)    // the plans of the in-process ranks must agree on every count
         for (int g = 0; g <= C + 1; ++g)
             for (int q = 0; q < P; ++q)
                 for (int s = 0; s < P; ++s)
                     if (s != q && recv_count(*shares[q]->plan, g, s) != send_count(*shares[s]->plan, g, q))
-                        return comm_fail(SRG_ERR_INVALID, "group %d: rank %d receives %lld rows from %d, which sends %lld",
-                                         g, q, (long long)recv_count(*shares[q]->plan, g, s), s,
-                                         (long long)send_count(*shares[s]->plan, g, q));
+                        return srg_fail(SRG_ERR_INVALID, "group %d: rank %d receives %lld rows from %d, which sends %lld",
+                                        g, q, (long long)recv_count(*shares[q]->plan, g, s), s,
+                                        (long long)send_count(*shares[s]->plan, g, q));
     if (K == 0 || d == 0) return SRG_OK;
     const Rccl* r = nullptr;
     DeviceScope scope;
@@ -801,7 +781,7 @@ int srg_halo_propagate_f32(srg_comm* comm, srg_halo_share* const* shares, int n_
     if (!(flags & SRG_HALO_X_HALO_FILLED)) {
         for (int g = 0; g <= G; ++g) {
             for (int i = 0; i < n_shards; ++i) {
-                SRG_HIPC(hipSetDevice(shares[i]->device));
+                SRG_HIP_CHECK(hipSetDevice(shares[i]->device));
                 if ((rc = halo_pack(shares[i], g, panels[i][0], d, st(i)))) return rc;
             }
             if ((rc = halo_transport(r, comm, shares, n_shards, g, panel_k(0), d))) return rc;
@@ -819,7 +799,7 @@ int srg_halo_propagate_f32(srg_comm* comm, srg_halo_share* const* shares, int n_
         };
         // the hub group forked onto the library's side stream, beside the chunks
         for (int i = 0; i < n_shards; ++i) {
-            SRG_HIPC(hipSetDevice(shares[i]->device));
+            SRG_HIP_CHECK(hipSetDevice(shares[i]->device));
             if ((rc = launch(i, C, SRG_SPMM_HUB_NOJOIN))) return rc;
         }
         // a row chunk: one launch, or its column blocks in order (the share's, when d asks for as many)
@@ -841,14 +821,14 @@ int srg_halo_propagate_f32(srg_comm* comm, srg_halo_share* const* shares, int n_
         };
         for (int c = 0; c < C; ++c) {
             for (int i = 0; i < n_shards; ++i) {
-                SRG_HIPC(hipSetDevice(shares[i]->device));
+                SRG_HIP_CHECK(hipSetDevice(shares[i]->device));
                 if ((rc = chunk(i, c))) return rc;
                 if (ex && (rc = halo_pack(shares[i], c, panels[i][k], d, st(i)))) return rc;
             }
             if (ex && (rc = halo_transport(r, comm, shares, n_shards, c, panel_k(k), d))) return rc;
         }
         for (int i = 0; i < n_shards; ++i) {
-            SRG_HIPC(hipSetDevice(shares[i]->device));
+            SRG_HIP_CHECK(hipSetDevice(shares[i]->device));
             if (ex && (rc = launch(i, G, 0))) return rc;            // the ghost rows into their halo slots
             if (shares[i]->plan->views[C].n && (rc = srg_hub_join(st(i)))) return rc;
             if (ex && (rc = halo_pack(shares[i], C, panels[i][k], d, st(i)))) return rc;

@@ -21,7 +21,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,30 +29,10 @@
 #include <vector>
 
 #include "srg_halo_internal.h"
+#include "srg_internal.h"
 #include "srgnn_hip.h"
 
-extern "C" void srg_set_error(int code, const char* msg);   // srg_spmm.hip: thread-local srg_last_error
-extern "C" void srg_clear_error(void);
-
 namespace {
-
-int hfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    srg_set_error(code, buf);
-    return code;
-}
-
-#define SRG_HALO_HIP(expr)                                                                       \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return hfail(SRG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));            \
-    } while (0)
 
 // srgnn.dist.balanced_row_starts: row bounds s_0 = 0 <= ... <= s_parts = n with about equal nonzeros;
 // ip holds n + 1 row pointers, `base` is ip's value at the first row (a block of a larger CSR)
@@ -185,8 +164,8 @@ int build_blocks(srg_halo_share* S, int B)
     for (int b = 1; b < B; ++b) {
         if (rows == 0) continue;
         if (hipMalloc((void**)&K.splits[b - 1], (size_t)rows * sizeof(int64_t)) != hipSuccess)
-            return hfail(SRG_ERR_ALLOC, "column block split points (%lld rows)", (long long)rows);
-        SRG_HALO_HIP(hipMemcpy(K.splits[b - 1], sp[b - 1].data(), (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice));
+            return srg_fail(SRG_ERR_ALLOC, "column block split points (%lld rows)", (long long)rows);
+        SRG_HIP_CHECK(hipMemcpy(K.splits[b - 1], sp[b - 1].data(), (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice));
         K.bounds[b] = K.splits[b - 1];
     }
     K.orders.assign(C, std::vector<int32_t*>(B, nullptr));
@@ -195,8 +174,8 @@ int build_blocks(srg_halo_share* S, int B)
             std::vector<int32_t>& o = K.views[c][b].order;
             if (!o.empty()) {
                 if (hipMalloc((void**)&K.orders[c][b], o.size() * sizeof(int32_t)) != hipSuccess)
-                    return hfail(SRG_ERR_ALLOC, "column block schedule (%zu rows)", o.size());
-                SRG_HALO_HIP(hipMemcpy(K.orders[c][b], o.data(), o.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+                    return srg_fail(SRG_ERR_ALLOC, "column block schedule (%zu rows)", o.size());
+                SRG_HIP_CHECK(hipMemcpy(K.orders[c][b], o.data(), o.size() * sizeof(int32_t), hipMemcpyHostToDevice));
             }
             std::vector<int32_t>().swap(o);
         }
@@ -217,18 +196,18 @@ int srg_halo_plan_build(const int64_t* indptr, const int32_t* indices, int64_t n
                         int32_t chunks, int64_t hub_threshold, int64_t heavy_threshold, int32_t ghost_max_degree,
                         double link_bps, srg_halo_plan** out)
 {
-    if (!out) return hfail(SRG_ERR_INVALID, "null output handle");
+    if (!out) return srg_fail(SRG_ERR_INVALID, "null output handle");
     *out = nullptr;
-    if (!indptr || (n > 0 && !indices)) return hfail(SRG_ERR_INVALID, "null indptr / indices");
-    if (n < 0 || n > INT32_MAX - 1) return hfail(SRG_ERR_INVALID, "n=%lld out of range", (long long)n);
-    if (nranks < 1 || rank < 0 || rank >= nranks) return hfail(SRG_ERR_INVALID, "rank %d of %d", rank, nranks);
-    if (chunks < 1 || chunks > 250) return hfail(SRG_ERR_INVALID, "chunks=%d not in [1, 250]", chunks);
+    if (!indptr || (n > 0 && !indices)) return srg_fail(SRG_ERR_INVALID, "null indptr / indices");
+    if (n < 0 || n > INT32_MAX - 1) return srg_fail(SRG_ERR_INVALID, "n=%lld out of range", (long long)n);
+    if (nranks < 1 || rank < 0 || rank >= nranks) return srg_fail(SRG_ERR_INVALID, "rank %d of %d", rank, nranks);
+    if (chunks < 1 || chunks > 250) return srg_fail(SRG_ERR_INVALID, "chunks=%d not in [1, 250]", chunks);
     const bool auto_ghost = ghost_max_degree == SRG_HALO_AUTO;
     if (ghost_max_degree < 0 && !auto_ghost)
-        return hfail(SRG_ERR_INVALID, "ghost_max_degree=%d < 0 (SRG_HALO_AUTO: the cost model)", ghost_max_degree);
+        return srg_fail(SRG_ERR_INVALID, "ghost_max_degree=%d < 0 (SRG_HALO_AUTO: the cost model)", ghost_max_degree);
     if (hub_threshold < SRG_HALO_NONE || heavy_threshold < SRG_HALO_AUTO)
-        return hfail(SRG_ERR_INVALID, "thresholds: hub %lld, heavy %lld", (long long)hub_threshold, (long long)heavy_threshold);
-    if (indptr[0] != 0) return hfail(SRG_ERR_INVALID, "indptr[0] = %lld != 0", (long long)indptr[0]);
+        return srg_fail(SRG_ERR_INVALID, "thresholds: hub %lld, heavy %lld", (long long)hub_threshold, (long long)heavy_threshold);
+    if (indptr[0] != 0) return srg_fail(SRG_ERR_INVALID, "indptr[0] = %lld != 0", (long long)indptr[0]);
     {
         // the checks in parallel pieces; the first violation (lowest position) is reported
         std::vector<int64_t> bad_row((size_t)plan_threads() + 1, INT64_MAX);
@@ -240,7 +219,7 @@ int srg_halo_plan_build(const int64_t* indptr, const int32_t* indices, int64_t n
             bad_row[(size_t)slot++] = b;
         });
         const int64_t b = *std::min_element(bad_row.begin(), bad_row.end());
-        if (b != INT64_MAX) return hfail(SRG_ERR_INVALID, "indptr decreases at row %lld", (long long)b);
+        if (b != INT64_MAX) return srg_fail(SRG_ERR_INVALID, "indptr decreases at row %lld", (long long)b);
     }
     const int64_t nnz = indptr[n];
     {
@@ -254,11 +233,11 @@ int srg_halo_plan_build(const int64_t* indptr, const int32_t* indices, int64_t n
         });
         const int64_t e = *std::min_element(bad_e.begin(), bad_e.end());
         if (e != INT64_MAX)
-            return hfail(SRG_ERR_INVALID, "column id %d at entry %lld outside [0, %lld)", indices[e], (long long)e, (long long)n);
+            return srg_fail(SRG_ERR_INVALID, "column id %d at entry %lld outside [0, %lld)", indices[e], (long long)e, (long long)n);
     }
 
     srg_halo_plan* P_ = new (std::nothrow) srg_halo_plan();
-    if (!P_) return hfail(SRG_ERR_ALLOC, "out of host memory");
+    if (!P_) return srg_fail(SRG_ERR_ALLOC, "out of host memory");
     srg_halo_plan& pl = *P_;
     const int P = nranks, p = rank, C = chunks, G = C + 1;
     pl.P = P; pl.p = p; pl.C = C; pl.n = n; pl.nnz_total = nnz;
@@ -443,7 +422,7 @@ int srg_halo_plan_build(const int64_t* indptr, const int32_t* indices, int64_t n
         });
         if (miss) {
             delete P_;
-            return hfail(SRG_ERR_INVALID, "halo layout misses a referenced column");
+            return srg_fail(SRG_ERR_INVALID, "halo layout misses a referenced column");
         }
     }
     pl.halo_ids.reserve(pl.halo);
@@ -475,8 +454,7 @@ int srg_halo_plan_build(const int64_t* indptr, const int32_t* indices, int64_t n
         if (!auto_h) V.n_heavy_narrow = V.n_heavy;
     }
     *out = P_;
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 int srg_halo_plan_destroy(srg_halo_plan* plan)
@@ -487,7 +465,7 @@ int srg_halo_plan_destroy(srg_halo_plan* plan)
 
 int srg_halo_plan_info(const srg_halo_plan* plan, srg_halo_info* info)
 {
-    if (!plan || !info) return hfail(SRG_ERR_INVALID, "null argument");
+    if (!plan || !info) return srg_fail(SRG_ERR_INVALID, "null argument");
     const srg_halo_plan& pl = *plan;
     info->row0 = pl.r0;
     info->n_rows = pl.rows;
@@ -509,7 +487,7 @@ int srg_halo_plan_info(const srg_halo_plan* plan, srg_halo_info* info)
 
 int srg_halo_plan_array(const srg_halo_plan* plan, int32_t what, int32_t index, const void** data, int64_t* count)
 {
-    if (!plan || !data || !count) return hfail(SRG_ERR_INVALID, "null argument");
+    if (!plan || !data || !count) return srg_fail(SRG_ERR_INVALID, "null argument");
     const srg_halo_plan& pl = *plan;
     const int G = pl.C + 1;
     auto put = [&](const auto& v) { *data = v.data(); *count = (int64_t)v.size(); return SRG_OK; };
@@ -529,7 +507,7 @@ int srg_halo_plan_array(const srg_halo_plan* plan, int32_t what, int32_t index, 
     default: break;
     }
     if (what == SRG_HALO_VIEW_ORDER || what == SRG_HALO_VIEW_META) {
-        if (index < 0 || index > G) return hfail(SRG_ERR_INVALID, "view %d of %d", index, G + 1);
+        if (index < 0 || index > G) return srg_fail(SRG_ERR_INVALID, "view %d of %d", index, G + 1);
         const SrgHaloView& V = pl.views[index];
         if (what == SRG_HALO_VIEW_ORDER) return put(V.order);
         meta[0] = V.n; meta[1] = V.n_hub; meta[2] = V.n_heavy; meta[3] = V.n_heavy_narrow;
@@ -537,38 +515,38 @@ int srg_halo_plan_array(const srg_halo_plan* plan, int32_t what, int32_t index, 
         *count = 4;
         return SRG_OK;
     }
-    if (index < 0 || index >= G) return hfail(SRG_ERR_INVALID, "group %d of %d", index, G);
+    if (index < 0 || index >= G) return srg_fail(SRG_ERR_INVALID, "group %d of %d", index, G);
     switch (what) {
     case SRG_HALO_SEND_ROWS: return put(pl.send_cat[index]);
     case SRG_HALO_SEND_COUNTS: return put(pl.send_counts[index]);
     case SRG_HALO_RECV_COUNTS: return put(pl.recv_counts[index]);
-    default: return hfail(SRG_ERR_INVALID, "unknown plan array %d", what);
+    default: return srg_fail(SRG_ERR_INVALID, "unknown plan array %d", what);
     }
 }
 
 int srg_halo_share_create(const srg_halo_plan* plan, const float* values, int device, int32_t d_max,
                           srg_halo_share** out)
 {
-    if (!out) return hfail(SRG_ERR_INVALID, "null output handle");
+    if (!out) return srg_fail(SRG_ERR_INVALID, "null output handle");
     *out = nullptr;
-    if (!plan || (plan->nnz_total > 0 && !values)) return hfail(SRG_ERR_INVALID, "null plan / values");
-    if (d_max < 1) return hfail(SRG_ERR_INVALID, "d_max=%d < 1", d_max);
+    if (!plan || (plan->nnz_total > 0 && !values)) return srg_fail(SRG_ERR_INVALID, "null plan / values");
+    if (d_max < 1) return srg_fail(SRG_ERR_INVALID, "d_max=%d < 1", d_max);
     const srg_halo_plan& pl = *plan;
     int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) return hfail(SRG_ERR_HIP, "no HIP device");
-    SRG_HALO_HIP(hipSetDevice(device));
+    if (hipGetDevice(&prev) != hipSuccess) return srg_fail(SRG_ERR_HIP, "no HIP device");
+    SRG_HIP_CHECK(hipSetDevice(device));
     struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
     srg_halo_share* S = new (std::nothrow) srg_halo_share();
-    if (!S) return hfail(SRG_ERR_ALLOC, "out of host memory");
+    if (!S) return srg_fail(SRG_ERR_ALLOC, "out of host memory");
     S->device = device;
     S->plan = plan;
     S->d_cap = d_max;
     auto fail_free = [&](int rc) { srg_halo_share_destroy(S); return rc; };
     auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
         if (bytes == 0) return SRG_OK;
-        if (hipMalloc(dst, bytes) != hipSuccess) return hfail(SRG_ERR_ALLOC, "hipMalloc(%zu) failed", bytes);
+        if (hipMalloc(dst, bytes) != hipSuccess) return srg_fail(SRG_ERR_ALLOC, "hipMalloc(%zu) failed", bytes);
         if (hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess)
-            return hfail(SRG_ERR_HIP, "hipMemcpy of %zu bytes failed", bytes);
+            return srg_fail(SRG_ERR_HIP, "hipMemcpy of %zu bytes failed", bytes);
         return SRG_OK;
     };
     // the local values: the own rows' entries, then the ghost rows' (host gather of the global array)
@@ -594,19 +572,18 @@ int srg_halo_share_create(const srg_halo_plan* plan, const float* values, int de
     if (rc) return fail_free(rc);
     if (S->send_off.back() > 0 &&
         hipMalloc((void**)&S->sendbuf, (size_t)S->send_off.back() * (size_t)d_max * sizeof(float)) != hipSuccess)
-        return fail_free(hfail(SRG_ERR_ALLOC, "send buffer of %lld rows x %d", (long long)S->send_off.back(), d_max));
+        return fail_free(srg_fail(SRG_ERR_ALLOC, "send buffer of %lld rows x %d", (long long)S->send_off.back(), d_max));
     const int B = srg_halo_col_blocks(pl.rows + pl.halo, d_max);
     if (B > 1 && (rc = build_blocks(S, B))) return fail_free(rc);
     S->packed.assign(G + 1, nullptr);
     for (auto& e : S->packed)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
-            return fail_free(hfail(SRG_ERR_HIP, "hipEventCreate failed"));
+            return fail_free(srg_fail(SRG_ERR_HIP, "hipEventCreate failed"));
     if (hipEventCreateWithFlags(&S->comm_done, hipEventDisableTiming) != hipSuccess ||
         hipStreamCreateWithFlags(&S->comm_stream, hipStreamNonBlocking) != hipSuccess)
-        return fail_free(hfail(SRG_ERR_HIP, "comm stream / event creation failed"));
+        return fail_free(srg_fail(SRG_ERR_HIP, "comm stream / event creation failed"));
     *out = S;
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 int srg_halo_share_destroy(srg_halo_share* S)
@@ -633,14 +610,14 @@ int srg_halo_share_destroy(srg_halo_share* S)
 
 int srg_halo_share_col_blocks(srg_halo_share* S, int32_t n_blocks)
 {
-    if (!S || !S->plan) return hfail(SRG_ERR_INVALID, "null share");
+    if (!S || !S->plan) return srg_fail(SRG_ERR_INVALID, "null share");
     if (n_blocks != SRG_HALO_AUTO && (n_blocks < 1 || n_blocks > 64))
-        return hfail(SRG_ERR_INVALID, "n_blocks=%d not in [1, 64] nor SRG_HALO_AUTO", n_blocks);
+        return srg_fail(SRG_ERR_INVALID, "n_blocks=%d not in [1, 64] nor SRG_HALO_AUTO", n_blocks);
     int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) return hfail(SRG_ERR_HIP, "no HIP device");
-    SRG_HALO_HIP(hipSetDevice(S->device));
+    if (hipGetDevice(&prev) != hipSuccess) return srg_fail(SRG_ERR_HIP, "no HIP device");
+    SRG_HIP_CHECK(hipSetDevice(S->device));
     struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
-    SRG_HALO_HIP(hipDeviceSynchronize());          // no launch of this share may still read the old arrays
+    SRG_HIP_CHECK(hipDeviceSynchronize());          // no launch of this share may still read the old arrays
     free_blocks(S->blocks);
     const srg_halo_plan& pl = *S->plan;
     const int B = n_blocks == SRG_HALO_AUTO ? srg_halo_col_blocks(pl.rows + pl.halo, (int)S->d_cap) : n_blocks;
@@ -650,32 +627,31 @@ int srg_halo_share_col_blocks(srg_halo_share* S, int32_t n_blocks)
         return rc;
     }
     S->blocks.forced = n_blocks != SRG_HALO_AUTO;
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 int srg_halo_fill_x_halo(const srg_halo_share* S, const float* X, int64_t ldx, float* panel0, int64_t ld, int32_t d,
                          void* stream)
 {
-    if (!S || !X || !panel0) return hfail(SRG_ERR_INVALID, "null argument");
+    if (!S || !X || !panel0) return srg_fail(SRG_ERR_INVALID, "null argument");
     const srg_halo_plan& pl = *S->plan;
-    if (ld < d || ldx < d) return hfail(SRG_ERR_INVALID, "leading dimensions < d");
+    if (ld < d || ldx < d) return srg_fail(SRG_ERR_INVALID, "leading dimensions < d");
     // own rows, then the halo rows gathered by global id (the ids live on the host: one upload)
     int64_t* ids = nullptr;
     int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) return hfail(SRG_ERR_HIP, "no HIP device");
-    SRG_HALO_HIP(hipSetDevice(S->device));
+    if (hipGetDevice(&prev) != hipSuccess) return srg_fail(SRG_ERR_HIP, "no HIP device");
+    SRG_HIP_CHECK(hipSetDevice(S->device));
     struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (pl.rows)
-        SRG_HALO_HIP(hipMemcpy2DAsync(panel0, (size_t)ld * 4, X + pl.r0 * ldx, (size_t)ldx * 4, (size_t)d * 4,
+        SRG_HIP_CHECK(hipMemcpy2DAsync(panel0, (size_t)ld * 4, X + pl.r0 * ldx, (size_t)ldx * 4, (size_t)d * 4,
                                       (size_t)pl.rows, hipMemcpyDeviceToDevice, s));
     if (pl.halo == 0) return SRG_OK;
-    SRG_HALO_HIP(hipMallocAsync((void**)&ids, (size_t)pl.halo * sizeof(int64_t), s));
-    SRG_HALO_HIP(hipMemcpyAsync(ids, pl.halo_ids.data(), (size_t)pl.halo * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    SRG_HIP_CHECK(hipMallocAsync((void**)&ids, (size_t)pl.halo * sizeof(int64_t), s));
+    SRG_HIP_CHECK(hipMemcpyAsync(ids, pl.halo_ids.data(), (size_t)pl.halo * sizeof(int64_t), hipMemcpyHostToDevice, s));
     int rc = srg_gather_rows_f32(X, ldx, pl.n, ids, pl.halo, panel0 + pl.rows * ld, ld, d, stream);
-    SRG_HALO_HIP(hipFreeAsync(ids, s));
-    SRG_HALO_HIP(hipStreamSynchronize(s));      // the host id array is pageable: keep it alive
+    SRG_HIP_CHECK(hipFreeAsync(ids, s));
+    SRG_HIP_CHECK(hipStreamSynchronize(s));      // the host id array is pageable: keep it alive
     return rc;
 }
 

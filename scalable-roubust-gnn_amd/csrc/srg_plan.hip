@@ -25,13 +25,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <new>
 #include <vector>
 
 #include "srgnn_hip.h"
 
+#include "srg_internal.h"
 #include "srg_plan_internal.h"
 
 struct srg_plan {
@@ -96,24 +96,6 @@ struct srg_plan {
 };
 
 namespace {
-
-int pfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    srg_set_error(code, buf);
-    return code;
-}
-
-#define SRG_PLAN_HIP(expr)                                                                       \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return pfail(SRG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));            \
-    } while (0)
 
 // The layout's constants (DESIGN.md §5.1 has the measurements behind each; srgnn.csr keeps kWholeMax and
 // the narrow threshold for the halo planner's chunks and the one-launch schedule of a DeviceCSR)
@@ -630,23 +612,6 @@ unsigned grid_for(int64_t work, int per_block, unsigned cap)
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(g, cap));
 }
 
-struct DevGuard {
-    int prev = -1, rc = SRG_OK;
-    explicit DevGuard(hipStream_t s)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; return; }
-        if (!s) return;
-        hipDevice_t d = 0;
-        if (hipStreamGetDevice(s, &d) != hipSuccess) { rc = pfail(SRG_ERR_HIP, "hipStreamGetDevice failed"); return; }
-        if ((int)d != prev && hipSetDevice((int)d) != hipSuccess) rc = pfail(SRG_ERR_HIP, "hipSetDevice(%d) failed", (int)d);
-    }
-    ~DevGuard()
-    {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // build temporaries: released after the work enqueued on `s` so far
 struct DevBuf {
     void* p = nullptr;
@@ -761,11 +726,11 @@ int complete_rows(srg_plan* P, hipStream_t s)
     tab[nl] = P->n_items;
     DevBuf t;
     t.s = s;
-    SRG_PLAN_HIP(hipMalloc(&t.p, tab.size() * sizeof(int64_t)));
-    SRG_PLAN_HIP(hipMemcpyAsync(t.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    SRG_HIP_CHECK(hipMalloc(&t.p, tab.size() * sizeof(int64_t)));
+    SRG_HIP_CHECK(hipMemcpyAsync(t.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     const srg_plan::Launch& L0 = P->launches[0];
     hipLaunchKernelGGL(k_plan_rows, dim3(grid_for(P->n_items, 256, 1u << 20)), dim3(256), 0, s, P->n, L0.order, (const int64_t*)t.p, nl, L0.slot_beg, L0.slot_end, P->n_items, P->blk_beg, P->blk_end);
-    SRG_PLAN_HIP(hipGetLastError());
+    SRG_HIP_CHECK(hipGetLastError());
     P->rows_full = true;
     note_use(P, s);
     return SRG_OK;
@@ -790,7 +755,7 @@ int scan_i64(In in, int64_t n, int64_t* out, bool inclusive, int64_t* part, hipS
     hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(kScanThreads), 0, s, part, tiles);
     hipLaunchKernelGGL(k_scan_apply<In>, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, in, n, (const int64_t*)part,
                        out, inclusive ? 1 : 0);
-    SRG_PLAN_HIP(hipGetLastError());
+    SRG_HIP_CHECK(hipGetLastError());
     return SRG_OK;
 }
 
@@ -812,13 +777,13 @@ int radix_sort_pairs(uint64_t* keys, int32_t* vals, uint64_t* skeys, int32_t* sv
         if (rc) return rc;
         hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)tiles), dim3(kSortThreads), 0, s, ki, vi, ko, vo, n, shift,
                            dmask, tiles, (const int64_t*)hist);
-        SRG_PLAN_HIP(hipGetLastError());
+        SRG_HIP_CHECK(hipGetLastError());
         std::swap(ki, ko);
         std::swap(vi, vo);
     }
     if (ki != skeys) {
-        SRG_PLAN_HIP(hipMemcpyAsync(skeys, ki, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-        SRG_PLAN_HIP(hipMemcpyAsync(svals, vi, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        SRG_HIP_CHECK(hipMemcpyAsync(skeys, ki, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+        SRG_HIP_CHECK(hipMemcpyAsync(svals, vi, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     }
     return SRG_OK;
 }
@@ -847,29 +812,28 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
                int32_t hops, int32_t col_blocks, int64_t hub_threshold, int64_t heavy_threshold, uint32_t opts,
                void* stream, srg_plan** plan, const BuildMem& mem)
 {
-    if (!plan && !mem.query()) return pfail(SRG_ERR_INVALID, "null plan");
+    if (!plan && !mem.query()) return srg_fail(SRG_ERR_INVALID, "null plan");
     if (plan) *plan = nullptr;
-    if (!indptr) return pfail(SRG_ERR_INVALID, "null indptr");
-    if (n_rows < 0 || n_rows >= (1ll << 31)) return pfail(SRG_ERR_INVALID, "n_rows=%lld outside [0, 2^31)", (long long)n_rows);
+    if (!indptr) return srg_fail(SRG_ERR_INVALID, "null indptr");
+    if (n_rows < 0 || n_rows >= (1ll << 31)) return srg_fail(SRG_ERR_INVALID, "n_rows=%lld outside [0, 2^31)", (long long)n_rows);
     if (d <= 0 || hops < 0 || col_blocks < 0 || col_blocks > kMaxBlocks)
-        return pfail(SRG_ERR_INVALID, "d=%d, hops=%d, col_blocks=%d (0 = automatic, at most %d)", d, hops, col_blocks, kMaxBlocks);
+        return srg_fail(SRG_ERR_INVALID, "d=%d, hops=%d, col_blocks=%d (0 = automatic, at most %d)", d, hops, col_blocks, kMaxBlocks);
     if (hub_threshold < SRG_PLAN_NONE || heavy_threshold < SRG_PLAN_NONE)
-        return pfail(SRG_ERR_INVALID, "hub_threshold=%lld, heavy_threshold=%lld: a row length, SRG_PLAN_AUTO or SRG_PLAN_NONE",
-                     (long long)hub_threshold, (long long)heavy_threshold);
+        return srg_fail(SRG_ERR_INVALID, "hub_threshold=%lld, heavy_threshold=%lld: a row length, SRG_PLAN_AUTO or SRG_PLAN_NONE",
+                        (long long)hub_threshold, (long long)heavy_threshold);
     const uint32_t known = SRG_PLAN_COMPACT | SRG_PLAN_SPANS | SRG_PLAN_SPLIT_BLOCK0 | SRG_PLAN_WHOLE_BLOCK0 |
                            SRG_PLAN_WHOLE_HUBS | (0xffffu << SRG_PLAN_WHOLE_MAX_SHIFT);
     // block 0's whole rows: at most this many entries (SRG_PLAN_WHOLE_MAX(n); 0: kWholeMax)
     const int64_t whole_max = (opts >> SRG_PLAN_WHOLE_MAX_SHIFT) ? (int64_t)(opts >> SRG_PLAN_WHOLE_MAX_SHIFT) : kWholeMax;
     if ((opts & ~known) || ((opts & SRG_PLAN_COMPACT) && (opts & SRG_PLAN_SPANS)) ||
         ((opts & SRG_PLAN_SPLIT_BLOCK0) && (opts & SRG_PLAN_WHOLE_BLOCK0)))
-        return pfail(SRG_ERR_INVALID, "opts=0x%x: unknown or conflicting options", opts);
+        return srg_fail(SRG_ERR_INVALID, "opts=0x%x: unknown or conflicting options", opts);
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    DevGuard g(s);
-    if (g.rc) return g.rc;
+    SRG_DEVICE_GUARD(s);
     srg_plan* P = new (std::nothrow) srg_plan();
-    if (!P) return pfail(SRG_ERR_ALLOC, "plan: host memory");
+    if (!P) return srg_fail(SRG_ERR_ALLOC, "plan: host memory");
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { delete P; return pfail(SRG_ERR_HIP, "hipGetDevice failed"); }
+    if (hipGetDevice(&dev) != hipSuccess) { delete P; return srg_fail(SRG_ERR_HIP, "hipGetDevice failed"); }
     P->device = dev;
     P->n = n_rows;
     P->d = d;
@@ -883,21 +847,21 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
     {
         DevBuf st;
         st.s = s;
-        if (hipMalloc(&st.p, 4 * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return bail(pfail(SRG_ERR_ALLOC, "plan: statistics")); }
+        if (hipMalloc(&st.p, 4 * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return bail(srg_fail(SRG_ERR_ALLOC, "plan: statistics")); }
         unsigned long long* dstats = (unsigned long long*)st.p;
-        if (hipMemsetAsync(dstats, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return bail(pfail(SRG_ERR_HIP, "memset"));
+        if (hipMemsetAsync(dstats, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return bail(srg_fail(SRG_ERR_HIP, "memset"));
         hipLaunchKernelGGL(k_plan_stats, dim3(grid_for(std::max<int64_t>(n, 1), 256, 512)), dim3(256), 0, s, indptr, n, whole_max,
                            dstats);
         if (hipMemcpyAsync(hs, dstats, sizeof(hs), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return bail(pfail(SRG_ERR_HIP, "plan: degree statistics: %s", hipGetErrorString(hipGetLastError())));
+            return bail(srg_fail(SRG_ERR_HIP, "plan: degree statistics: %s", hipGetErrorString(hipGetLastError())));
     }
     const int64_t max_deg = (int64_t)hs[0], n_whole_rows = (int64_t)hs[1];
     const int64_t nnz = (int64_t)hs[3] - (int64_t)hs[2];
     unsigned long long* dstat = nullptr;     // (reused below for the whole hub rows' count)
-    if (nnz < 0) return bail(pfail(SRG_ERR_INVALID, "indptr[n] < indptr[0]"));
+    if (nnz < 0) return bail(srg_fail(SRG_ERR_INVALID, "indptr[n] < indptr[0]"));
     // values may be NULL for a SPANS plan (fp64 Chebyshev steps bring their own values: srg_plan_cheby_step_f64)
     if (nnz > 0 && !mem.query() && (!indices || (!values && !(opts & SRG_PLAN_SPANS))))
-        return bail(pfail(SRG_ERR_INVALID, "null indices / values"));
+        return bail(srg_fail(SRG_ERR_INVALID, "null indices / values"));
     P->nnz = nnz;
     P->no_values = nnz > 0 && !values;
     // ---- 2: the layout: blocks, launches, copies ----
@@ -935,12 +899,12 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
         DevBuf st;
         st.s = s;
         unsigned long long hc = 0;
-        if (hipMalloc(&st.p, sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return bail(pfail(SRG_ERR_ALLOC, "plan: statistics")); }
+        if (hipMalloc(&st.p, sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return bail(srg_fail(SRG_ERR_ALLOC, "plan: statistics")); }
         dstat = (unsigned long long*)st.p;
-        if (hipMemsetAsync(dstat, 0, sizeof(unsigned long long), s) != hipSuccess) return bail(pfail(SRG_ERR_HIP, "memset"));
+        if (hipMemsetAsync(dstat, 0, sizeof(unsigned long long), s) != hipSuccess) return bail(srg_fail(SRG_ERR_HIP, "memset"));
         hipLaunchKernelGGL(k_plan_count_above, dim3(grid_for(n, 256, 512)), dim3(256), 0, s, indptr, n, hubw_t, dstat);
         if (hipMemcpyAsync(&hc, dstat, sizeof(hc), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return bail(pfail(SRG_ERR_HIP, "plan: hub rows: %s", hipGetErrorString(hipGetLastError())));
+            return bail(srg_fail(SRG_ERR_HIP, "plan: hub rows: %s", hipGetErrorString(hipGetLastError())));
         n_hubw = (int64_t)hc;
         if (!n_hubw) hubw_t = INT64_MAX;
     }
@@ -973,7 +937,7 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
     }
     const int64_t n_items = T.off[T.n_launch];
     P->n_items = n_items;
-    if (T.lenbits + T.lbits > 64) return bail(pfail(SRG_ERR_INVALID, "row lengths too long to plan"));
+    if (T.lenbits + T.lbits > 64) return bail(srg_fail(SRG_ERR_INVALID, "row lengths too long to plan"));
     if (mem.query()) {
         *mem.q_opts = (compact ? SRG_PLAN_COMPACT : SRG_PLAN_SPANS) | (split0 ? SRG_PLAN_SPLIT_BLOCK0 : SRG_PLAN_WHOLE_BLOCK0) |
                       (opts & (SRG_PLAN_WHOLE_HUBS | (0xffffu << SRG_PLAN_WHOLE_MAX_SHIFT)));
@@ -982,14 +946,12 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
             *mem.q_keep = 0;
             *mem.q_scratch = 0;
             delete P;
-            srg_clear_error();
-            return SRG_OK;
+            return srg_ok();
         }
     }
     if (n == 0) {
         *plan = P;
-        srg_clear_error();
-        return SRG_OK;
+        return srg_ok();
     }
     // the two allocations: what the plan keeps, the build's scratch (sizes first, then carved)
     const bool slots = B > 1 || compact;   // a one-launch CSR hop reads no slot spans
@@ -1035,17 +997,16 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
                 *mem.q_keep = keep.used;
                 *mem.q_scratch = tmp.used;
                 delete P;
-                srg_clear_error();
-                return SRG_OK;
+                return srg_ok();
             }
             P->bytes = (int64_t)keep.used;
             if (mem.caller()) {
                 // the caller's memory: 256-byte aligned (the arena's pieces are), large enough
                 if (((uintptr_t)mem.keep & 255) || ((uintptr_t)mem.scratch & 255) || !mem.scratch ||
                     mem.keep_bytes < keep.used || mem.scratch_bytes < tmp.used)
-                    return bail(pfail(SRG_ERR_INVALID, "plan: caller memory keep %zu of %zu bytes, scratch %zu of %zu "
-                                      "(srg_plan_query's sizes, 256-byte aligned)", mem.keep_bytes, keep.used,
-                                      mem.scratch_bytes, tmp.used));
+                    return bail(srg_fail(SRG_ERR_INVALID, "plan: caller memory keep %zu of %zu bytes, scratch %zu of %zu "
+                                         "(srg_plan_query's sizes, 256-byte aligned)", mem.keep_bytes, keep.used,
+                                         mem.scratch_bytes, tmp.used));
                 P->owned = mem.keep;
                 P->owns = false;
                 scratch_base = (char*)mem.scratch;
@@ -1054,12 +1015,12 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
             if (hipMalloc(&P->owned, keep.used) != hipSuccess) {
                 (void)hipGetLastError();
                 P->owned = nullptr;
-                return bail(pfail(SRG_ERR_ALLOC, "plan: %zu bytes of device memory", keep.used));
+                return bail(srg_fail(SRG_ERR_ALLOC, "plan: %zu bytes of device memory", keep.used));
             }
             if (hipMalloc(&scratch.p, tmp.used) != hipSuccess) {
                 (void)hipGetLastError();
                 scratch.p = nullptr;
-                return bail(pfail(SRG_ERR_ALLOC, "plan: %zu bytes of build scratch", tmp.used));
+                return bail(srg_fail(SRG_ERR_ALLOC, "plan: %zu bytes of build scratch", tmp.used));
             }
             scratch_base = (char*)scratch.p;
         }
@@ -1072,7 +1033,7 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
         if (rc) return bail(rc);
     }
     // the sort items, sorted by (launch, decreasing span length)
-    SRG_PLAN_HIP(hipMemsetAsync(keys, 0xff, (size_t)n_items * sizeof(uint64_t), s));
+    SRG_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)n_items * sizeof(uint64_t), s));
     hipLaunchKernelGGL(k_plan_items, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, indptr, splits, cutpos, n, B,
                        split0 ? 1 : 0, T, keys, vals);
     {
@@ -1081,28 +1042,28 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
     }
     {
         // pos[i] = the entries of the items before i (launch-major): copy positions and launch nnz
-        SRG_PLAN_HIP(hipMemsetAsync(pos, 0, sizeof(int64_t), s));
+        SRG_HIP_CHECK(hipMemsetAsync(pos, 0, sizeof(int64_t), s));
         const int rc = scan_i64(KeyLen{skeys, (1ull << T.lenbits) - 1}, n_items, pos + 1, true, ptmp, s);
         if (rc) return bail(rc);
     }
     // ---- 3: per-launch counts and the guard (host sync 2) ----
-    SRG_PLAN_HIP(hipMemsetAsync(dcounts + 4 * T.n_launch, 0, sizeof(int64_t), s));
+    SRG_HIP_CHECK(hipMemsetAsync(dcounts + 4 * T.n_launch, 0, sizeof(int64_t), s));
     hipLaunchKernelGGL(k_plan_check, dim3(grid_for(n_items, 256, 4096)), dim3(256), 0, s, skeys, n_items, T,
                        (int32_t*)(dcounts + 4 * T.n_launch));
     hipLaunchKernelGGL(k_plan_counts, dim3(1), dim3(128), 0, s, skeys, order, pos, T, dcounts, dhubs);
     std::vector<int64_t> counts((size_t)4 * T.n_launch + 1);
     std::vector<int32_t> hubs((size_t)kHubPrefix * T.n_launch);
-    SRG_PLAN_HIP(hipMemcpyAsync(counts.data(), dcounts, counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    SRG_PLAN_HIP(hipMemcpyAsync(hubs.data(), dhubs, hubs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SRG_HIP_CHECK(hipMemcpyAsync(counts.data(), dcounts, counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SRG_HIP_CHECK(hipMemcpyAsync(hubs.data(), dhubs, hubs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     {
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return bail(pfail(SRG_ERR_HIP, "plan build: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return bail(srg_fail(SRG_ERR_HIP, "plan build: %s", hipGetErrorString(e)));
         int64_t total = 0;
         for (int L = 0; L < T.n_launch; ++L) total += counts[4 * L];
         if (counts[4 * T.n_launch] != 0 || total != nnz)
-            return bail(pfail(SRG_ERR_INVALID, "plan build: inconsistent layout (%lld of %lld entries placed%s)",
-                              (long long)total, (long long)nnz, counts[4 * T.n_launch] ? ", items outside their launch" : ""));
+            return bail(srg_fail(SRG_ERR_INVALID, "plan build: inconsistent layout (%lld of %lld entries placed%s)",
+                                 (long long)total, (long long)nnz, counts[4 * T.n_launch] ? ", items outside their launch" : ""));
     }
     // ---- 4: the spans the launches read ----
     // compact: row-indexed spans for the rows the packed-row width reads them for (hub and slice-wave
@@ -1120,7 +1081,7 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
                            nnz, oix, ov);
     {
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return bail(pfail(SRG_ERR_HIP, "plan build: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return bail(srg_fail(SRG_ERR_HIP, "plan build: %s", hipGetErrorString(e)));
     }
     // ---- 5: the launch descriptors ----
     for (int L = 0; L < T.n_launch; ++L) {
@@ -1177,12 +1138,11 @@ static int build_impl(const int64_t* indptr, const int32_t* indices, const float
     scratch.reset();
     if (mem.caller()) {
         const hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return bail(pfail(SRG_ERR_HIP, "plan build: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return bail(srg_fail(SRG_ERR_HIP, "plan build: %s", hipGetErrorString(e)));
     }
     note_use(P, s);
     *plan = P;
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 extern "C" {
@@ -1200,7 +1160,7 @@ int srg_plan_query(const int64_t* indptr, int64_t n_rows, int32_t d, int32_t hop
                    size_t* scratch_bytes, uint32_t* resolved_opts, int32_t* resolved_col_blocks)
 {
     if (!keep_bytes || !scratch_bytes || !resolved_opts || !resolved_col_blocks)
-        return pfail(SRG_ERR_INVALID, "null output");
+        return srg_fail(SRG_ERR_INVALID, "null output");
     BuildMem m;
     m.q_keep = keep_bytes;
     m.q_scratch = scratch_bytes;
@@ -1217,7 +1177,7 @@ int srg_plan_build_in(const int64_t* indptr, const int32_t* indices, const float
                       void* keep, size_t keep_bytes, void* scratch, size_t scratch_bytes, void* stream,
                       srg_plan** plan)
 {
-    if (!keep) return pfail(SRG_ERR_INVALID, "null keep memory (srg_plan_build allocates its own)");
+    if (!keep) return srg_fail(SRG_ERR_INVALID, "null keep memory (srg_plan_build allocates its own)");
     BuildMem m;
     m.keep = keep;
     m.keep_bytes = keep_bytes;
@@ -1231,8 +1191,11 @@ int srg_plan_destroy(srg_plan* plan, void* stream)
 {
     if (!plan) return SRG_OK;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    DevGuard g(s);
-    if (!s) (void)hipSetDevice(plan->device);
+    DeviceGuard g(s);
+    if (!s) {   // the null stream: the plan's device, for the guard to restore from
+        (void)hipSetDevice(plan->device);
+        g.dev = plan->device;
+    }
     // hub rows a caller driving the launches itself (srg_plan_launch) left on the side stream of `s`
     (void)srg_hub_join(stream);
     release(plan, s);
@@ -1242,7 +1205,7 @@ int srg_plan_destroy(srg_plan* plan, void* stream)
 
 int srg_plan_describe(const srg_plan* plan, srg_plan_desc* desc)
 {
-    if (!plan || !desc) return pfail(SRG_ERR_INVALID, "null plan / desc");
+    if (!plan || !desc) return srg_fail(SRG_ERR_INVALID, "null plan / desc");
     desc->n_rows = plan->n;
     desc->nnz = plan->nnz;
     desc->device_bytes = plan->bytes;
@@ -1254,8 +1217,7 @@ int srg_plan_describe(const srg_plan* plan, srg_plan_desc* desc)
     desc->hub_chain = (plan->B > 1 && plan->same_hubs && plan->block_hubs) ? 1 : 0;
     desc->hub_rows_whole = (int32_t)plan->n_hub_whole;
     desc->device = plan->device;
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 // A caller that repeats a propagate (the same panels, widths, hops, flags and stream) gets the K hops as
@@ -1311,13 +1273,12 @@ static int plan_launches(const srg_plan* P, int32_t d, uint32_t flags, std::vect
 
 int srg_plan_launch(const srg_plan* plan, int32_t i, int32_t d, srg_hop_launch* launch, int32_t* join_hub, void* stream)
 {
-    if (!plan || !launch) return pfail(SRG_ERR_INVALID, "null plan / launch");
+    if (!plan || !launch) return srg_fail(SRG_ERR_INVALID, "null plan / launch");
     if (i < 0 || i >= (int32_t)plan->launches.size() || d <= 0)
-        return pfail(SRG_ERR_INVALID, "launch %d of %zu, d=%d", i, plan->launches.size(), d);
+        return srg_fail(SRG_ERR_INVALID, "launch %d of %zu, d=%d", i, plan->launches.size(), d);
     if (!plan->rows_full) {
         // a caller driving the launches may run any width: every row-indexed span, on `stream`
-        DevGuard g(static_cast<hipStream_t>(stream));
-        if (g.rc) return g.rc;
+        SRG_DEVICE_GUARD(stream);
         const int rc = complete_rows(const_cast<srg_plan*>(plan), static_cast<hipStream_t>(stream));
         if (rc) return rc;
     }
@@ -1325,26 +1286,24 @@ int srg_plan_launch(const srg_plan* plan, int32_t i, int32_t d, srg_hop_launch* 
     const int join = plan_launches(plan, d, 0, L);
     *launch = L[(size_t)i];
     if (join_hub) *join_hub = join;
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 int srg_plan_propagate_f32(const srg_plan* plan, float* const* panels, int64_t ld, int32_t d, int32_t K, uint32_t flags,
                            void* stream)
 {
-    if (!plan) return pfail(SRG_ERR_INVALID, "null plan");
+    if (!plan) return srg_fail(SRG_ERR_INVALID, "null plan");
     if (flags & ~(SRG_SPMM_NT_STORE | SRG_SPMM_FAST))
-        return pfail(SRG_ERR_INVALID, "flags=0x%x: a plan's hops take NT_STORE and FAST only", flags);
+        return srg_fail(SRG_ERR_INVALID, "flags=0x%x: a plan's hops take NT_STORE and FAST only", flags);
     if (plan->no_values)
-        return pfail(SRG_ERR_INVALID, "the plan was built without fp32 values (SRG_PLAN_SPANS, values NULL): it serves "
-                     "srg_plan_cheby_step_f64 only");
-    if (d <= 0 || K < 0) return pfail(SRG_ERR_INVALID, "d=%d, K=%d", d, K);
-    if (K == 0 || plan->launches.empty()) { srg_clear_error(); return SRG_OK; }
-    DevGuard g(static_cast<hipStream_t>(stream));
-    if (g.rc) return g.rc;
+        return srg_fail(SRG_ERR_INVALID, "the plan was built without fp32 values (SRG_PLAN_SPANS, values NULL): it serves "
+                        "srg_plan_cheby_step_f64 only");
+    if (d <= 0 || K < 0) return srg_fail(SRG_ERR_INVALID, "d=%d, K=%d", d, K);
+    if (K == 0 || plan->launches.empty()) { return srg_ok(); }
+    SRG_DEVICE_GUARD(stream);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
-        return pfail(SRG_ERR_INVALID, "the plan lives on device %d, the stream on %d", plan->device, dev);
+        return srg_fail(SRG_ERR_INVALID, "the plan lives on device %d, the stream on %d", plan->device, dev);
     if (!plan->rows_full) {
         // the packed light rows (spans by slot) run only at 64 / 128 / 256 columns on 16-byte rows
         bool packed = packed_width(d) && ld % 4 == 0;
@@ -1375,11 +1334,10 @@ int srg_plan_propagate_f32(const srg_plan* plan, float* const* panels, int64_t l
             G.off = false;
         }
         auto replay = [&]() {
-            SRG_PLAN_HIP(hipGraphLaunch(G.exec, s));
-            SRG_PLAN_HIP(hipEventRecord(G.done, s));
+            SRG_HIP_CHECK(hipGraphLaunch(G.exec, s));
+            SRG_HIP_CHECK(hipEventRecord(G.done, s));
             note_use(P, s);
-            srg_clear_error();
-            return SRG_OK;
+            return srg_ok();
         };
         if (G.exec) return replay();
         if (G.calls >= 1 && !G.off) {
@@ -1413,27 +1371,25 @@ int srg_plan_propagate_f32(const srg_plan* plan, float* const* panels, int64_t l
 int srg_plan_hop_f32(const srg_plan* plan, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d,
                      uint32_t flags, float* agg, int64_t lda, float w, int32_t agg_init, void* stream)
 {
-    if (!plan) return pfail(SRG_ERR_INVALID, "null plan");
+    if (!plan) return srg_fail(SRG_ERR_INVALID, "null plan");
     if (flags & ~(SRG_SPMM_NT_STORE | SRG_SPMM_FAST))
-        return pfail(SRG_ERR_INVALID, "flags=0x%x: a plan's hops take NT_STORE and FAST only", flags);
+        return srg_fail(SRG_ERR_INVALID, "flags=0x%x: a plan's hops take NT_STORE and FAST only", flags);
     if (plan->no_values)
-        return pfail(SRG_ERR_INVALID, "the plan was built without fp32 values (SRG_PLAN_SPANS, values NULL): it serves "
-                     "srg_plan_cheby_step_f64 only");
+        return srg_fail(SRG_ERR_INVALID, "the plan was built without fp32 values (SRG_PLAN_SPANS, values NULL): it serves "
+                        "srg_plan_cheby_step_f64 only");
     if ((flags & SRG_SPMM_FAST) && agg)
-        return pfail(SRG_ERR_INVALID, "FAST takes no aggregation epilogue");
-    if (d <= 0 || ldx < d || ldy < d) return pfail(SRG_ERR_INVALID, "d=%d, ldx=%lld, ldy=%lld", d, (long long)ldx, (long long)ldy);
+        return srg_fail(SRG_ERR_INVALID, "FAST takes no aggregation epilogue");
+    if (d <= 0 || ldx < d || ldy < d) return srg_fail(SRG_ERR_INVALID, "d=%d, ldx=%lld, ldy=%lld", d, (long long)ldx, (long long)ldy);
     if (plan->launches.empty()) {
         // no rows: nothing to write
-        srg_clear_error();
-        return SRG_OK;
+        return srg_ok();
     }
-    if (!X || !Y) return pfail(SRG_ERR_INVALID, "null X / Y");
-    if (agg && lda < d) return pfail(SRG_ERR_INVALID, "lda=%lld < d=%d", (long long)lda, d);
-    DevGuard g(static_cast<hipStream_t>(stream));
-    if (g.rc) return g.rc;
+    if (!X || !Y) return srg_fail(SRG_ERR_INVALID, "null X / Y");
+    if (agg && lda < d) return srg_fail(SRG_ERR_INVALID, "lda=%lld < d=%d", (long long)lda, d);
+    SRG_DEVICE_GUARD(stream);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
-        return pfail(SRG_ERR_INVALID, "the plan lives on device %d, the stream on %d", plan->device, dev);
+        return srg_fail(SRG_ERR_INVALID, "the plan lives on device %d, the stream on %d", plan->device, dev);
     if (!plan->rows_full) {
         // the packed light rows run only at 64 / 128 / 256 columns on 16-byte rows (agg's too)
         const bool packed = packed_width(d) && ldx % 4 == 0 && ldy % 4 == 0 && (uintptr_t)X % 16 == 0 &&
@@ -1466,26 +1422,24 @@ int srg_plan_hop_f32(const srg_plan* plan, const float* X, int64_t ldx, float* Y
         rc = srg_hop_accumulate_f32(agg, lda, Y, ldy, plan->n, d, w, agg_init ? SRG_ACC_INIT : SRG_ACC_ADD, stream);
         if (rc) return rc;
     }
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 int srg_plan_cheby_step_f64(const srg_plan* plan, const double* values, const double* Tc, const double* To, double* Tn,
                             int64_t ld, int32_t d, int mode, double a1, double a2, const double* coef_prev,
                             const double* coef, int32_t n_scales, double* R, int64_t r_stride, void* stream)
 {
-    if (!plan) return pfail(SRG_ERR_INVALID, "null plan");
+    if (!plan) return srg_fail(SRG_ERR_INVALID, "null plan");
     if (plan->compact)
-        return pfail(SRG_ERR_INVALID, "an fp64 step reads spans of the caller's arrays: build the plan with SRG_PLAN_SPANS");
+        return srg_fail(SRG_ERR_INVALID, "an fp64 step reads spans of the caller's arrays: build the plan with SRG_PLAN_SPANS");
     if (plan->B > 1 && !plan->split0)
-        return pfail(SRG_ERR_INVALID, "an fp64 step needs block 0 as two launches: build the plan with SRG_PLAN_SPLIT_BLOCK0");
-    if (plan->launches.empty()) { srg_clear_error(); return SRG_OK; }
-    if (!values && plan->nnz > 0) return pfail(SRG_ERR_INVALID, "null values");
-    DevGuard g(static_cast<hipStream_t>(stream));
-    if (g.rc) return g.rc;
+        return srg_fail(SRG_ERR_INVALID, "an fp64 step needs block 0 as two launches: build the plan with SRG_PLAN_SPLIT_BLOCK0");
+    if (plan->launches.empty()) { return srg_ok(); }
+    if (!values && plan->nnz > 0) return srg_fail(SRG_ERR_INVALID, "null values");
+    SRG_DEVICE_GUARD(stream);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
-        return pfail(SRG_ERR_INVALID, "the plan lives on device %d, the stream on %d", plan->device, dev);
+        return srg_fail(SRG_ERR_INVALID, "the plan lives on device %d, the stream on %d", plan->device, dev);
     std::vector<srg_hop_launch> L;
     (void)plan_launches(plan, d, 0, L);
     std::vector<uint8_t> roles(L.size(), 0);
@@ -1501,8 +1455,7 @@ int srg_plan_cheby_step_f64(const srg_plan* plan, const double* values, const do
                                           ld, d, mode, a1, a2, coef_prev, coef, n_scales, R, r_stride, stream);
     if (rc) return rc;
     note_use(const_cast<srg_plan*>(plan), static_cast<hipStream_t>(stream));
-    srg_clear_error();
-    return SRG_OK;
+    return srg_ok();
 }
 
 }  // extern "C"

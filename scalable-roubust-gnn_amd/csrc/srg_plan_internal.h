@@ -10,9 +10,6 @@
 
 extern "C" {
 
-// srg_spmm.hip: thread-local srg_last_error
-void srg_set_error(int code, const char* msg);
-
 // One fp32 hop over a plan's launches (X -> Y), the aggregation epilogue on the launches agg_on marks.
 int srg_run_plan_hop(const srg_hop_launch* launches, int32_t n_launch, int32_t join_hub, const float* X,
                      int64_t ldx, float* Y, int64_t ldy, int32_t d, const uint8_t* agg_on, float* agg,

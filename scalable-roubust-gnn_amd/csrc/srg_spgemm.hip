@@ -23,54 +23,13 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
+#include "srg_internal.h"
 #include "srgnn_hip.h"
 
-extern "C" void srg_set_error(int code, const char* msg);   // srg_spmm.hip: thread-local srg_last_error
-extern "C" void srg_clear_error(void);
-
 namespace {
-
-int sg_fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    srg_set_error(code, buf);
-    return code;
-}
-
-int sg_ok()
-{
-    srg_clear_error();
-    return SRG_OK;
-}
-
-#define SG_HIP(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return sg_fail(SRG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-    } while (0)
-
-struct DeviceOf {          // the device of `s` current for the call (the null stream: the current one)
-    int prev = -1, rc = SRG_OK;
-    explicit DeviceOf(hipStream_t s)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; return; }
-        if (!s) return;
-        hipDevice_t d = 0;
-        if (hipStreamGetDevice(s, &d) != hipSuccess) { rc = sg_fail(SRG_ERR_HIP, "hipStreamGetDevice failed"); return; }
-        if ((int)d != prev && hipSetDevice((int)d) != hipSuccess) rc = sg_fail(SRG_ERR_HIP, "hipSetDevice failed");
-        else if ((int)d == prev) prev = -1;
-    }
-    ~DeviceOf() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // dense accumulator in LDS up to this many columns: 64 KiB of sums + 2 KiB of bitmap = 66 KiB, which
 // fits only because gfx950 gives a workgroup up to 160 KiB of LDS (the 64 KiB of earlier CDNA parts
@@ -205,15 +164,15 @@ extern "C" {
 
 int srg_spgemm_scratch_bytes(int64_t m, int64_t n_cols, int64_t* bytes)
 {
-    if (!bytes || m < 0 || n_cols < 0) return sg_fail(SRG_ERR_INVALID, "bad arguments");
+    if (!bytes || m < 0 || n_cols < 0) return srg_fail(SRG_ERR_INVALID, "bad arguments");
     if (n_cols <= kLdsCols) {
         *bytes = 0;
-        return sg_ok();
+        return srg_ok();
     }
     const int64_t per = 4 * n_cols + 4 * ((n_cols + 31) >> 5);
     const int64_t slots = m < kMaxGlobalSlots ? (m > 0 ? m : 1) : kMaxGlobalSlots;
     *bytes = slots * per;
-    return sg_ok();
+    return srg_ok();
 }
 
 int srg_spgemm_f32(int phase, const int64_t* a_ptr, const int32_t* a_idx, const float* a_val, int64_t m,
@@ -221,20 +180,19 @@ int srg_spgemm_f32(int phase, const int64_t* a_ptr, const int32_t* a_idx, const 
                    int64_t* c_cnt, const int64_t* c_ptr, int32_t* c_idx, float* c_val, void* scratch,
                    int64_t scratch_bytes, uint32_t flags, void* stream)
 {
-    if (phase != 0 && phase != 1) return sg_fail(SRG_ERR_INVALID, "phase %d", phase);
-    if (m < 0 || n_cols < 0 || n_cols > INT32_MAX) return sg_fail(SRG_ERR_INVALID, "bad shape m=%lld n=%lld",
+    if (phase != 0 && phase != 1) return srg_fail(SRG_ERR_INVALID, "phase %d", phase);
+    if (m < 0 || n_cols < 0 || n_cols > INT32_MAX) return srg_fail(SRG_ERR_INVALID, "bad shape m=%lld n=%lld",
                                                                    (long long)m, (long long)n_cols);
-    if (m == 0) return sg_ok();
+    if (m == 0) return srg_ok();
     if (!a_ptr || !b_ptr || (phase == 0 && !c_cnt) || (phase == 1 && !c_ptr))
-        return sg_fail(SRG_ERR_INVALID, "null pointer");
-    DeviceOf dev(static_cast<hipStream_t>(stream));
-    if (dev.rc) return dev.rc;
+        return srg_fail(SRG_ERR_INVALID, "null pointer");
+    SRG_DEVICE_GUARD(stream);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int serial = (flags & SRG_SPGEMM_SERIAL_B) ? 1 : 0;
     if (n_cols <= kLdsCols) {
         const size_t lds = 4 * (size_t)((n_cols + 3) & ~int64_t(3)) + 4 * (size_t)((n_cols + 31) >> 5);
         if (lds > 48 * 1024)
-            SG_HIP(hipFuncSetAttribute((const void*)k_spgemm<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+            SRG_HIP_CHECK(hipFuncSetAttribute((const void*)k_spgemm<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds));
         const int64_t grid = m < 16384 ? m : 16384;
         hipLaunchKernelGGL(k_spgemm<true>, dim3((unsigned)grid), dim3(kWave), lds, s, a_ptr, a_idx, a_val, m,
@@ -243,27 +201,26 @@ int srg_spgemm_f32(int phase, const int64_t* a_ptr, const int32_t* a_idx, const 
     } else {
         const int64_t per = 4 * n_cols + 4 * ((n_cols + 31) >> 5);
         const int64_t slots = scratch ? scratch_bytes / per : 0;
-        if (slots < 1) return sg_fail(SRG_ERR_INVALID, "scratch of %lld bytes < one accumulator (%lld)",
-                                      (long long)scratch_bytes, (long long)per);
+        if (slots < 1) return srg_fail(SRG_ERR_INVALID, "scratch of %lld bytes < one accumulator (%lld)",
+                                       (long long)scratch_bytes, (long long)per);
         const int64_t grid = slots < m ? slots : m;
         float* acc = static_cast<float*>(scratch);
         uint32_t* bits = reinterpret_cast<uint32_t*>(acc + grid * n_cols);
-        SG_HIP(hipMemsetAsync(scratch, 0, (size_t)(grid * per), s));
+        SRG_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(grid * per), s));
         hipLaunchKernelGGL(k_spgemm<false>, dim3((unsigned)grid), dim3(kWave), 0, s, a_ptr, a_idx, a_val, m,
                            b_ptr, b_idx, b_val, n_cols, phase, c_cnt, c_ptr, c_idx, c_val, acc, bits, serial);
     }
-    SG_HIP(hipGetLastError());
-    return sg_ok();
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
 }
 
 int srg_spmm_muladd_f32(const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows,
                         const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d, void* stream)
 {
-    if (n_rows < 0 || d < 0 || ldx < d || ldy < d) return sg_fail(SRG_ERR_INVALID, "bad shape");
-    if (n_rows == 0 || d == 0) return sg_ok();
-    if (!indptr || !Y) return sg_fail(SRG_ERR_INVALID, "null pointer");
-    DeviceOf dev(static_cast<hipStream_t>(stream));
-    if (dev.rc) return dev.rc;
+    if (n_rows < 0 || d < 0 || ldx < d || ldy < d) return srg_fail(SRG_ERR_INVALID, "bad shape");
+    if (n_rows == 0 || d == 0) return srg_ok();
+    if (!indptr || !Y) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    SRG_DEVICE_GUARD(stream);
     const int64_t blocks = (n_rows + 3) / 4;
     for (int64_t b0 = 0; b0 < blocks; b0 += (int64_t)1 << 23) {     // < 2^31 work-items per launch
         const int64_t nb = blocks - b0 < ((int64_t)1 << 23) ? blocks - b0 : ((int64_t)1 << 23);
@@ -271,8 +228,8 @@ int srg_spmm_muladd_f32(const int64_t* indptr, const int32_t* indices, const flo
         hipLaunchKernelGGL(k_spmm_muladd, dim3((unsigned)nb), dim3(256), 0, static_cast<hipStream_t>(stream),
                            indptr + r0, indices, values, n_rows - r0, X, ldx, Y + r0 * ldy, ldy, d);
     }
-    SG_HIP(hipGetLastError());
-    return sg_ok();
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
 }
 
 }  // extern "C"

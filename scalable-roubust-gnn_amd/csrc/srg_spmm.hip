@@ -34,21 +34,22 @@
 #include <vector>
 
 #include "srgnn_hip.h"
+#include "srg_internal.h"
 #include "srg_plan_internal.h"
 
 #ifndef SRG_GIT_REV
 #define SRG_GIT_REV "dev"
 #endif
 
+// ------------------------------------------------------------------------------------------------
+// error handling and the device guard (srg_internal.h): the library's one definition of each
+// ------------------------------------------------------------------------------------------------
 namespace {
-
-// ------------------------------------------------------------------------------------------------
-// error handling
-// ------------------------------------------------------------------------------------------------
 thread_local char g_err_msg[512] = "";
 thread_local int g_err_code = SRG_OK;
+}  // namespace
 
-int fail(int code, const char* fmt, ...)
+int srg_fail(int code, const char* fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -58,19 +59,38 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
-int ok()
+int srg_ok()
 {
     g_err_code = SRG_OK;
     g_err_msg[0] = '\0';
     return SRG_OK;
 }
 
-#define SRG_HIP_CHECK(expr)                                                                     \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(SRG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));            \
-    } while (0)
+DeviceGuard::DeviceGuard(hipStream_t s)
+{
+    // no usable device: leave it to the entry point (argument checks and empty problems
+    // need none; its first HIP call reports the error)
+    hipError_t e = hipGetDevice(&prev);
+    if (e != hipSuccess) { (void)hipGetLastError(); prev = -1; return; }
+    dev = prev;
+    if (s) {
+        hipDevice_t d = 0;
+        e = hipStreamGetDevice(s, &d);
+        if (e != hipSuccess) { rc = srg_fail(SRG_ERR_HIP, "hipStreamGetDevice failed: %s", hipGetErrorString(e)); return; }
+        dev = (int)d;
+    }
+    if (dev != prev) {
+        e = hipSetDevice(dev);
+        if (e != hipSuccess) { rc = srg_fail(SRG_ERR_HIP, "hipSetDevice(%d) failed: %s", dev, hipGetErrorString(e)); dev = prev; }
+    }
+}
+
+DeviceGuard::~DeviceGuard()
+{
+    if (prev >= 0 && dev != prev) (void)hipSetDevice(prev);
+}
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------
 // vector helpers
@@ -312,6 +332,17 @@ struct Epi {
     const int64_t* slot_beg;
     const int64_t* slot_end;
 };
+
+// The aggregation epilogue's fields (agg = (init ? 0 : agg) + w * Y), everything else off.
+inline Epi agg_epi(float* agg, int64_t lda, float w, int agg_init)
+{
+    Epi e{};
+    e.agg = agg;
+    e.lda = lda;
+    e.w = w;
+    e.init = agg_init ? 1 : 0;
+    return e;
+}
 
 // Epilogue kinds (template parameter EX of the SpMM kernels).  Every call site sits under
 // `if constexpr`: a runtime branch cost the plain kernels ~20 %, and even an empty inlined call
@@ -1849,7 +1880,7 @@ int side_stream_locked(hipStream_t caller, SideStream** out)
 {
     int dev = 0;
     SRG_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(SRG_ERR_HIP, "device id %d", dev);
+    if (dev < 0 || dev >= 64) return srg_fail(SRG_ERR_HIP, "device id %d", dev);
     if (!g_side_attr[dev]) {
         int rc = hub_attrs<int>();
         if (!rc) rc = hub_attrs<int64_t>();
@@ -1892,38 +1923,71 @@ int side_stream_locked(hipStream_t caller, SideStream** out)
     return SRG_OK;
 }
 
-// Makes the device of `s` current for the lifetime of the guard (the null stream means the
-// current device), so every launch, event and side stream of an entry point belongs to the
-// device the caller's stream lives on.
-struct DeviceGuard {
-    int prev = -1, dev = -1, rc = SRG_OK;
-    explicit DeviceGuard(hipStream_t s)
+// One launch's fork of hub work onto the side stream of (current device, caller stream), step by step:
+// fork, the hub launches on stream(), record_join, delay, the main launches, join.  Holds g_side_mu from
+// the first fork until it goes out of scope (the end of the launch: see SideStream), and makes no HIP call
+// when it does, so an error return only releases the lock.  A launch without hub rows never forks and
+// never takes the lock.
+class HubFork {
+public:
+    explicit HubFork(hipStream_t caller) : s_(caller), lock_(g_side_mu, std::defer_lock) {}
+    // Orders the side stream after the caller's stream.  may_continue: when the entry has an unjoined
+    // fork, no new one is made (continued()): the hub work is appended to the side stream as it is.
+    // Forking again on one object forks again under the lock it already holds.
+    int fork(bool may_continue = false)
     {
-        // no usable device: leave it to the entry point (argument checks and empty problems
-        // need none; its first HIP call reports the error)
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { (void)hipGetLastError(); prev = -1; return; }
-        dev = prev;
-        if (s) {
-            hipDevice_t d = 0;
-            e = hipStreamGetDevice(s, &d);
-            if (e != hipSuccess) { rc = fail(SRG_ERR_HIP, "hipStreamGetDevice failed: %s", hipGetErrorString(e)); return; }
-            dev = (int)d;
+        if (!lock_.owns_lock()) lock_.lock();
+        if (!ss_) {
+            int rc = side_stream_locked(s_, &ss_);
+            if (rc) return rc;
         }
-        if (dev != prev) {
-            e = hipSetDevice(dev);
-            if (e != hipSuccess) { rc = fail(SRG_ERR_HIP, "hipSetDevice(%d) failed: %s", dev, hipGetErrorString(e)); dev = prev; }
-        }
+        continued_ = may_continue && ss_->pending;
+        if (continued_) return SRG_OK;
+        SRG_HIP_CHECK(hipEventRecord(ss_->fork, s_));
+        SRG_HIP_CHECK(hipStreamWaitEvent(ss_->stream, ss_->fork, 0));
+        return SRG_OK;
     }
-    ~DeviceGuard()
+    bool continued() const { return continued_; }
+    hipStream_t stream() const { return ss_->stream; }
+    // After the hub launches; pending: the join is left to srg_hub_join.
+    int record_join(bool pending)
     {
-        if (prev >= 0 && dev != prev) (void)hipSetDevice(prev);
+        SRG_HIP_CHECK(hipEventRecord(ss_->join, ss_->stream));
+        ss_->pending = pending;
+        return SRG_OK;
     }
+    // The single-wave delay on the caller's stream (k_dispatch_delay)
+    int delay()
+    {
+        hipLaunchKernelGGL(k_dispatch_delay, dim3(1), dim3(64), 0, s_, kHubDelayUs);
+        SRG_HIP_CHECK(hipGetLastError());
+        return SRG_OK;
+    }
+    // The caller's stream waits for the recorded join (nothing to wait for without a fork).
+    int join()
+    {
+        if (ss_) SRG_HIP_CHECK(hipStreamWaitEvent(s_, ss_->join, 0));
+        return SRG_OK;
+    }
+
+private:
+    hipStream_t s_;
+    std::unique_lock<std::mutex> lock_;
+    SideStream* ss_ = nullptr;
+    bool continued_ = false;
 };
 
-#define SRG_DEVICE_GUARD(stream)                                   \
-    DeviceGuard guard_(static_cast<hipStream_t>(stream));          \
-    if (guard_.rc) return guard_.rc
+// Joins the side stream of (dev, s) into `s`: waits on the entry's join event -- only_pending: only after
+// an unjoined fork; otherwise whenever the entry has one -- and marks it joined.
+int join_side_stream(int dev, hipStream_t s, bool only_pending)
+{
+    std::lock_guard<std::mutex> lock(g_side_mu);
+    auto it = g_side.find(std::make_pair(dev, s));
+    if (it == g_side.end() || !(only_pending ? it->second.pending : it->second.join != nullptr)) return SRG_OK;
+    SRG_HIP_CHECK(hipStreamWaitEvent(s, it->second.join, 0));
+    it->second.pending = false;
+    return SRG_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // SRG_SPMM_FAST: the hub rows as kFastSegs segments each.  Segment s of hub row h (row order[h]) is
@@ -1975,8 +2039,8 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
 {
     if (n_rows <= 0 || d <= 0) return SRG_OK;
     if (n_hub < 0 || n_heavy < 0 || n_hub + n_heavy > n_rows || ((n_hub + n_heavy) > 0 && !order))
-        return fail(SRG_ERR_INVALID, "n_hub=%lld n_heavy=%lld need a row_order and <= n_rows",
-                    (long long)n_hub, (long long)n_heavy);
+        return srg_fail(SRG_ERR_INVALID, "n_hub=%lld n_heavy=%lld need a row_order and <= n_rows",
+                        (long long)n_hub, (long long)n_heavy);
     // slice waves and hub blocks gather 16-byte chunks: they need d % 4 == 0 and aligned rows;
     // otherwise every row takes the row-wave path (same results)
     const bool slice_ok = d % 4 == 0 && ldx % 4 == 0 && aligned(X, 16);
@@ -1986,66 +2050,55 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
     }
     const int n_slices = (d + kSliceCols - 1) / kSliceCols;
     if ((n_hub + n_heavy) * (int64_t)n_slices > INT32_MAX - 64)
-        return fail(SRG_ERR_INVALID, "too many heavy slices");
+        return srg_fail(SRG_ERR_INVALID, "too many heavy slices");
     const int acc = (flags & SRG_SPMM_ACCUMULATE) ? 1 : 0;
     const int nt = (flags & SRG_SPMM_NT_STORE) ? 1 : 0;
     const bool sfull = d % kSliceCols == 0;
 
-    SideStream* ss = nullptr;
-    std::unique_lock<std::mutex> side_lock(g_side_mu, std::defer_lock);
+    HubFork hub(s);
+    const bool nojoin = (flags & SRG_SPMM_HUB_NOJOIN) != 0;
     const bool fast = (flags & SRG_SPMM_FAST) && (EX == kEpiPlain || EX == kEpiSpan) && !epi.agg;
     if (n_hub > 0 && fast) {   // fork: the hub rows' segments, then their sums, beside the main launch
-        side_lock.lock();
-        int rc = side_stream_locked(s, &ss);
-        if (rc) return rc;
-        SRG_HIP_CHECK(hipEventRecord(ss->fork, s));
-        SRG_HIP_CHECK(hipStreamWaitEvent(ss->stream, ss->fork, 0));
+        if (int rc = hub.fork()) return rc;
         const int64_t T = n_hub * kFastSegs;
         const int64_t ldp = (d + 3) & ~3;
         const size_t idx_bytes = ((size_t)T * (2 * sizeof(int64_t) + sizeof(int32_t)) + 255) & ~(size_t)255;
         void* buf = nullptr;
-        SRG_HIP_CHECK(hipMallocAsync(&buf, idx_bytes + (size_t)T * ldp * sizeof(float), ss->stream));
+        SRG_HIP_CHECK(hipMallocAsync(&buf, idx_bytes + (size_t)T * ldp * sizeof(float), hub.stream()));
         int64_t* seg_beg = static_cast<int64_t*>(buf);
         int64_t* seg_end = seg_beg + T;
         int32_t* seg_order = reinterpret_cast<int32_t*>(seg_end + T);
         float* part = reinterpret_cast<float*>(static_cast<char*>(buf) + idx_bytes);
         const unsigned gs = (unsigned)((T + 255) / 256);
         if (EX == kEpiSpan)
-            hipLaunchKernelGGL((k_fast_segments<IP, true>), dim3(gs), dim3(256), 0, ss->stream, indptr, epi.row_end,
+            hipLaunchKernelGGL((k_fast_segments<IP, true>), dim3(gs), dim3(256), 0, hub.stream(), indptr, epi.row_end,
                                order, n_hub, seg_beg, seg_end, seg_order);
         else
-            hipLaunchKernelGGL((k_fast_segments<IP, false>), dim3(gs), dim3(256), 0, ss->stream, indptr, nullptr,
+            hipLaunchKernelGGL((k_fast_segments<IP, false>), dim3(gs), dim3(256), 0, hub.stream(), indptr, nullptr,
                                order, n_hub, seg_beg, seg_end, seg_order);
         SRG_HIP_CHECK(hipGetLastError());
         Epi se{};
         se.row_end = seg_end;
-        // every segment a slice-wave row (exact chain over its span), no hubs, no accumulation
-        rc = launch_spmm<int64_t, kEpiSpan>(seg_beg, indices, vals, T, seg_order, 0, T, X, ldx, part, ldp, d,
-                                            flags & SRG_SPMM_PACKED_U2, ss->stream, se);
-        if (rc) return rc;
+        // every segment a slice-wave row (exact chain over its span), no hubs (so no fork of its own), no
+        // accumulation
+        if (int rc = launch_spmm<int64_t, kEpiSpan>(seg_beg, indices, vals, T, seg_order, 0, T, X, ldx, part, ldp, d,
+                                                    flags & SRG_SPMM_PACKED_U2, hub.stream(), se))
+            return rc;
         const unsigned gr = (unsigned)((n_hub * d + 255) / 256);
-        hipLaunchKernelGGL(k_fast_reduce, dim3(gr), dim3(256), 0, ss->stream, order, n_hub, part, ldp, Y, ldy, d, acc);
+        hipLaunchKernelGGL(k_fast_reduce, dim3(gr), dim3(256), 0, hub.stream(), order, n_hub, part, ldp, Y, ldy, d, acc);
         SRG_HIP_CHECK(hipGetLastError());
-        SRG_HIP_CHECK(hipFreeAsync(buf, ss->stream));
-        SRG_HIP_CHECK(hipEventRecord(ss->join, ss->stream));
-        ss->pending = (flags & SRG_SPMM_HUB_NOJOIN) != 0;
+        SRG_HIP_CHECK(hipFreeAsync(buf, hub.stream()));
+        if (int rc = hub.record_join(nojoin)) return rc;
     } else if (n_hub > 0) {   // fork: hub blocks run beside the main launch
-        side_lock.lock();
-        int rc = side_stream_locked(s, &ss);
-        if (rc) return rc;
         // CONTINUE after an unjoined fork: the hub rows are appended to the side stream, which is
         // already ordered after everything they read (the caller's guarantee), with no new fork
         // and no dispatch delay on the caller's stream
-        const bool cont = (flags & SRG_SPMM_HUB_CONTINUE) && ss->pending;
-        if (!cont) {
-            SRG_HIP_CHECK(hipEventRecord(ss->fork, s));
-            SRG_HIP_CHECK(hipStreamWaitEvent(ss->stream, ss->fork, 0));
-        }
+        if (int rc = hub.fork((flags & SRG_SPMM_HUB_CONTINUE) != 0)) return rc;
         const dim3 hgrid((unsigned)(n_hub * n_slices));
         // 256-nonzero windows (two workgroups per CU) once a launch has more hub workgroups than CUs
         const bool w256 = n_hub * n_slices > kHubWideLaunch || (flags & SRG_SPMM_HUB_W256);
 #define SRG_LAUNCH_HUB(SF, WW)                                                                                      \
-    hipLaunchKernelGGL((k_spmm_hub<SF, IP, EX, WW>), hgrid, dim3(kHubThreads), (HubGeom<WW>::LDS_BYTES), ss->stream, \
+    hipLaunchKernelGGL((k_spmm_hub<SF, IP, EX, WW>), hgrid, dim3(kHubThreads), (HubGeom<WW>::LDS_BYTES), hub.stream(), \
                        indptr, indices, vals, order, n_slices, X, ldx, Y, ldy, d, acc, nt, epi)
         if (sfull) {
             if (w256) SRG_LAUNCH_HUB(true, kHubWideW);
@@ -2056,12 +2109,9 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
         }
 #undef SRG_LAUNCH_HUB
         SRG_HIP_CHECK(hipGetLastError());
-        SRG_HIP_CHECK(hipEventRecord(ss->join, ss->stream));
-        ss->pending = (flags & SRG_SPMM_HUB_NOJOIN) != 0;
-        if (!cont) {
-            hipLaunchKernelGGL(k_dispatch_delay, dim3(1), dim3(64), 0, s, kHubDelayUs);
-            SRG_HIP_CHECK(hipGetLastError());
-        }
+        if (int rc = hub.record_join(nojoin)) return rc;
+        if (!hub.continued())
+            if (int rc = hub.delay()) return rc;
     }
 
     const int32_t* morder = order ? order + n_hub : nullptr;
@@ -2090,11 +2140,11 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
     if (xh) {
         const int64_t per = 8 / n_slices;
         const int64_t bh = ((n_heavy + kWavesPerBlock - 1) / kWavesPerBlock + per - 1) / per * 8;
-        if (bh > INT32_MAX) return fail(SRG_ERR_INVALID, "grid too large");
+        if (bh > INT32_MAX) return srg_fail(SRG_ERR_INVALID, "grid too large");
         nb_heavy_launch = (int)bh;
     }
     const int64_t blocks = nb_heavy_launch + (n_light + rows_per_block - 1) / rows_per_block;
-    if (blocks > INT32_MAX) return fail(SRG_ERR_INVALID, "grid too large");
+    if (blocks > INT32_MAX) return srg_fail(SRG_ERR_INVALID, "grid too large");
     int vec = pick_vec(d, ldx, ldy, X, Y, sizeof(float));
     if (epi.agg) vec = std::min(vec, pick_vec(d, epi.lda, epi.lda, epi.agg, epi.agg, sizeof(float)));
     if (EX == kEpiCheby) {
@@ -2171,21 +2221,20 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
 #undef SRG_LAUNCH_PACKED_U
         SRG_HIP_CHECK(hipGetLastError());
     }
-    if (ss && !(flags & SRG_SPMM_HUB_NOJOIN)) SRG_HIP_CHECK(hipStreamWaitEvent(s, ss->join, 0));   // join
-    return SRG_OK;
+    return nojoin ? SRG_OK : hub.join();
 }
 
 int check_spmm_args(const void* indptr, const void* indices, const void* vals, int64_t n_rows,
                     const void* X, int64_t ldx, const void* Y, int64_t ldy, int d)
 {
     if (n_rows < 0 || n_rows > INT32_MAX - 64)
-        return fail(SRG_ERR_INVALID, "n_rows=%lld out of range [0, 2^31-64)", (long long)n_rows);
-    if (d < 0) return fail(SRG_ERR_INVALID, "d=%d < 0", d);
+        return srg_fail(SRG_ERR_INVALID, "n_rows=%lld out of range [0, 2^31-64)", (long long)n_rows);
+    if (d < 0) return srg_fail(SRG_ERR_INVALID, "d=%d < 0", d);
     if (ldx < d || ldy < d)
-        return fail(SRG_ERR_INVALID, "leading dimensions (ldx=%lld, ldy=%lld) < d=%d",
-                    (long long)ldx, (long long)ldy, d);
+        return srg_fail(SRG_ERR_INVALID, "leading dimensions (ldx=%lld, ldy=%lld) < d=%d",
+                        (long long)ldx, (long long)ldy, d);
     if (n_rows > 0 && d > 0 && (!indptr || !Y))
-        return fail(SRG_ERR_INVALID, "null indptr or Y");
+        return srg_fail(SRG_ERR_INVALID, "null indptr or Y");
     (void)indices; (void)vals; (void)X;
     return SRG_OK;
 }
@@ -2193,22 +2242,31 @@ int check_spmm_args(const void* indptr, const void* indices, const void* vals, i
 // The fused step's mode and coefficients (cheby_epi_at): coef_prev holds c0 per scale (INIT) or c0 then c1
 // per scale (STEP_FIRST), coef c1 (INIT) or ck (STEP, STEP_FIRST); INIT_T takes neither; | SRG_CHEBY_NO_T.
 template <typename T>
-int cheby_setup(int mode, const T* coef_prev, const T* coef, int n_scales, const void* To, ChebyCoef<T>& cf)
+int cheby_coefs(int mode, const T* coef_prev, const T* coef, int n_scales, ChebyCoef<T>& cf)
 {
     const int m = mode & ~SRG_CHEBY_NO_T;
     if (m != SRG_CHEBY_INIT && m != SRG_CHEBY_STEP && m != SRG_CHEBY_INIT_T && m != SRG_CHEBY_STEP_FIRST)
-        return fail(SRG_ERR_INVALID, "cheby mode %d", mode);
-    if (n_scales < 1 || n_scales > 8) return fail(SRG_ERR_INVALID, "n_scales=%d not in [1,8]", n_scales);
+        return srg_fail(SRG_ERR_INVALID, "cheby mode %d", mode);
+    if (n_scales < 1 || n_scales > 8) return srg_fail(SRG_ERR_INVALID, "n_scales=%d not in [1,8]", n_scales);
     const bool needs_r = m != SRG_CHEBY_INIT_T;
     if ((needs_r && !coef) || ((m == SRG_CHEBY_INIT || m == SRG_CHEBY_STEP_FIRST) && !coef_prev))
-        return fail(SRG_ERR_INVALID, "null coefficient array");
-    if ((m == SRG_CHEBY_STEP || m == SRG_CHEBY_STEP_FIRST) && !To) return fail(SRG_ERR_INVALID, "null To for a step");
+        return srg_fail(SRG_ERR_INVALID, "null coefficient array");
     for (int i = 0; i < 8; ++i) {
         const bool on = i < n_scales;
         cf.prev[i] = ((m == SRG_CHEBY_INIT || m == SRG_CHEBY_STEP_FIRST) && on) ? T(0.5) * coef_prev[i] : T(0);
         cf.mid[i] = (m == SRG_CHEBY_STEP_FIRST && on) ? coef_prev[n_scales + i] : T(0);
         cf.cur[i] = (needs_r && on) ? coef[i] : T(0);
     }
+    return SRG_OK;
+}
+
+// cheby_coefs, and the To panel that a step reads
+template <typename T>
+int cheby_setup(int mode, const T* coef_prev, const T* coef, int n_scales, const void* To, ChebyCoef<T>& cf)
+{
+    if (int rc = cheby_coefs<T>(mode, coef_prev, coef, n_scales, cf)) return rc;
+    const int m = mode & ~SRG_CHEBY_NO_T;
+    if ((m == SRG_CHEBY_STEP || m == SRG_CHEBY_STEP_FIRST) && !To) return srg_fail(SRG_ERR_INVALID, "null To for a step");
     return SRG_OK;
 }
 
@@ -2233,30 +2291,23 @@ int launch_cheby(const int64_t* indptr, const int32_t* indices, const T* vals, i
     rc = check_spmm_args(indptr, indices, vals, n_rows, Tc, ld, Tn, ld, d);
     if (rc) return rc;
     if (r_stride < n_rows * ld && n_scales > 1)
-        return fail(SRG_ERR_INVALID, "r_stride too small for stacked scale panels");
+        return srg_fail(SRG_ERR_INVALID, "r_stride too small for stacked scale panels");
     if (n_hub < 0 || n_hub > n_rows || (n_hub > 0 && !order))
-        return fail(SRG_ERR_INVALID, "n_hub=%lld needs a row_order and <= n_rows", (long long)n_hub);
-    if (n_rows == 0 || d == 0) return ok();
+        return srg_fail(SRG_ERR_INVALID, "n_hub=%lld needs a row_order and <= n_rows", (long long)n_hub);
+    if (n_rows == 0 || d == 0) return srg_ok();
     // hub workgroups gather 16-byte pieces (two columns) of Tc's rows
     if (sizeof(T) != 8 || d % 2 || ld % 2 || !aligned(Tc, 16)) n_hub = 0;
     const int n_slices = (d + kHub64Cols - 1) / kHub64Cols;
-    if (n_hub * n_slices > INT32_MAX - 64) return fail(SRG_ERR_INVALID, "too many hub slices");
-    SideStream* ss = nullptr;
-    std::unique_lock<std::mutex> side_lock(g_side_mu, std::defer_lock);
+    if (n_hub * n_slices > INT32_MAX - 64) return srg_fail(SRG_ERR_INVALID, "too many hub slices");
+    HubFork hub(s);
     if constexpr (sizeof(T) == 8) {
         if (n_hub > 0) {   // fork: the hub rows' workgroups beside the row waves
-            side_lock.lock();
-            int rc = side_stream_locked(s, &ss);
-            if (rc) return rc;
-            SRG_HIP_CHECK(hipEventRecord(ss->fork, s));
-            SRG_HIP_CHECK(hipStreamWaitEvent(ss->stream, ss->fork, 0));
-            launch_hub64(n_hub * n_slices, ss->stream, indptr, indices, vals, order, n_slices, Tc, To, Tn, ld, d, mode,
+            if (int rc = hub.fork()) return rc;
+            launch_hub64(n_hub * n_slices, hub.stream(), indptr, indices, vals, order, n_slices, Tc, To, Tn, ld, d, mode,
                          a1, a2, cf, n_scales, R, r_stride);
             SRG_HIP_CHECK(hipGetLastError());
-            SRG_HIP_CHECK(hipEventRecord(ss->join, ss->stream));
-            ss->pending = nojoin;
-            hipLaunchKernelGGL(k_dispatch_delay, dim3(1), dim3(64), 0, s, kHubDelayUs);
-            SRG_HIP_CHECK(hipGetLastError());
+            if (int rc = hub.record_join(nojoin)) return rc;
+            if (int rc = hub.delay()) return rc;
         }
     }
     order = order ? order + n_hub : nullptr;
@@ -2280,8 +2331,9 @@ int launch_cheby(const int64_t* indptr, const int32_t* indices, const T* vals, i
         SRG_HIP_CHECK(hipGetLastError());
     }
     SRG_HIP_CHECK(hipGetLastError());
-    if (ss && !nojoin) SRG_HIP_CHECK(hipStreamWaitEvent(s, ss->join, 0));   // join
-    return ok();
+    if (!nojoin)
+        if (int rc = hub.join()) return rc;
+    return srg_ok();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2314,7 +2366,7 @@ int stage_reserve(int slot, size_t bytes, int dev)
     if (hipMalloc(&g_stage.buf[slot], want) != hipSuccess) {
         g_stage.buf[slot] = nullptr;
         (void)hipGetLastError();
-        return fail(SRG_ERR_ALLOC, "hipMalloc(%zu) failed", want);
+        return srg_fail(SRG_ERR_ALLOC, "hipMalloc(%zu) failed", want);
     }
     g_stage.cap[slot] = want;
     g_stage.device[slot] = dev;
@@ -2326,19 +2378,19 @@ int host_compat_spmm(float* answer, const float* data, const int* indices, const
                      const float* mat, int mat_row, int mat_col, bool overwrite, int64_t nnz_hint)
 {
     if (mat_row < 0 || mat_col < 0)
-        return fail(SRG_ERR_INVALID, "mat_row=%d mat_col=%d", mat_row, mat_col);
-    if (mat_row == 0 || mat_col == 0) return ok();
-    if (!answer || !indptr || !mat) return fail(SRG_ERR_INVALID, "null host pointer");
+        return srg_fail(SRG_ERR_INVALID, "mat_row=%d mat_col=%d", mat_row, mat_col);
+    if (mat_row == 0 || mat_col == 0) return srg_ok();
+    if (!answer || !indptr || !mat) return srg_fail(SRG_ERR_INVALID, "null host pointer");
     const int64_t nnz = indptr[mat_row];
-    if (indptr[0] != 0 || nnz < 0) return fail(SRG_ERR_INVALID, "indptr[0]=%d indptr[n]=%lld", indptr[0], (long long)nnz);
+    if (indptr[0] != 0 || nnz < 0) return srg_fail(SRG_ERR_INVALID, "indptr[0]=%d indptr[n]=%lld", indptr[0], (long long)nnz);
     if (nnz_hint >= 0 && nnz_hint != nnz)
-        return fail(SRG_ERR_INVALID, "data_nnz=%lld != indptr[mat_row]=%lld", (long long)nnz_hint, (long long)nnz);
+        return srg_fail(SRG_ERR_INVALID, "data_nnz=%lld != indptr[mat_row]=%lld", (long long)nnz_hint, (long long)nnz);
     for (int i = 0; i < mat_row; ++i)
-        if (indptr[i + 1] < indptr[i]) return fail(SRG_ERR_INVALID, "indptr decreases at row %d", i);
-    if (nnz > 0 && (!indices || !data)) return fail(SRG_ERR_INVALID, "null indices/data");
+        if (indptr[i + 1] < indptr[i]) return srg_fail(SRG_ERR_INVALID, "indptr decreases at row %d", i);
+    if (nnz > 0 && (!indices || !data)) return srg_fail(SRG_ERR_INVALID, "null indices/data");
     for (int64_t j = 0; j < nnz; ++j)
         if (indices[j] < 0 || indices[j] >= mat_row)
-            return fail(SRG_ERR_INVALID, "column id %d at %lld outside [0, %d)", indices[j], (long long)j, mat_row);
+            return srg_fail(SRG_ERR_INVALID, "column id %d at %lld outside [0, %d)", indices[j], (long long)j, mat_row);
 
     std::lock_guard<std::mutex> lock(g_stage.mu);
     int dev = 0;
@@ -2375,7 +2427,7 @@ int host_compat_spmm(float* answer, const float* data, const int* indices, const
     if (rc) return rc;
     SRG_HIP_CHECK(hipMemcpyAsync(answer, d_y, panel, hipMemcpyDeviceToHost, s));
     SRG_HIP_CHECK(hipStreamSynchronize(s));
-    return ok();
+    return srg_ok();
 }
 
 }  // namespace
@@ -2407,7 +2459,7 @@ int srg_spmm_csr_f32(const int64_t* indptr, const int32_t* indices, const float*
     if (rc) return rc;
     rc = launch_spmm<int64_t>(indptr, indices, values, n_rows, row_order, n_hub, n_heavy, X, ldx, Y, ldy, d, flags,
                               static_cast<hipStream_t>(stream));
-    return rc ? rc : ok();
+    return rc ? rc : srg_ok();
 }
 
 int srg_spmm_agg_f32(const int64_t* indptr, const int32_t* indices, const float* values,
@@ -2419,11 +2471,11 @@ int srg_spmm_agg_f32(const int64_t* indptr, const int32_t* indices, const float*
     int rc = check_spmm_args(indptr, indices, values, n_rows, X, ldx, Y, ldy, d);
     if (rc) return rc;
     if (n_rows > 0 && d > 0 && (!agg || lda < d))
-        return fail(SRG_ERR_INVALID, "aggregation panel: agg=%p lda=%lld < d=%d", (void*)agg, (long long)lda, d);
-    if (agg && agg == Y) return fail(SRG_ERR_INVALID, "agg must not alias Y");
+        return srg_fail(SRG_ERR_INVALID, "aggregation panel: agg=%p lda=%lld < d=%d", (void*)agg, (long long)lda, d);
+    if (agg && agg == Y) return srg_fail(SRG_ERR_INVALID, "agg must not alias Y");
     rc = launch_spmm<int64_t>(indptr, indices, values, n_rows, row_order, n_hub, n_heavy, X, ldx, Y, ldy, d, flags,
-                              static_cast<hipStream_t>(stream), Epi{agg, lda, w, agg_init ? 1 : 0});
-    return rc ? rc : ok();
+                              static_cast<hipStream_t>(stream), agg_epi(agg, lda, w, agg_init));
+    return rc ? rc : srg_ok();
 }
 
 int srg_spmm_span_f32(const int64_t* row_beg, const int64_t* row_end, const int32_t* indices,
@@ -2434,18 +2486,14 @@ int srg_spmm_span_f32(const int64_t* row_beg, const int64_t* row_end, const int3
     SRG_DEVICE_GUARD(stream);
     int rc = check_spmm_args(row_beg, indices, values, n_rows, X, ldx, Y, ldy, d);
     if (rc) return rc;
-    if (n_rows > 0 && d > 0 && !row_end) return fail(SRG_ERR_INVALID, "null row_end");
+    if (n_rows > 0 && d > 0 && !row_end) return srg_fail(SRG_ERR_INVALID, "null row_end");
     if (agg && (lda < d || agg == Y))
-        return fail(SRG_ERR_INVALID, "aggregation panel: lda=%lld < d=%d or agg aliases Y", (long long)lda, d);
-    Epi e{};
-    e.agg = agg;
-    e.lda = lda;
-    e.w = w;
-    e.init = agg_init ? 1 : 0;
+        return srg_fail(SRG_ERR_INVALID, "aggregation panel: lda=%lld < d=%d or agg aliases Y", (long long)lda, d);
+    Epi e = agg_epi(agg, lda, w, agg_init);
     e.row_end = row_end;
     rc = launch_spmm<int64_t, kEpiSpan>(row_beg, indices, values, n_rows, row_order, n_hub, n_heavy, X, ldx, Y, ldy,
                                         d, flags, static_cast<hipStream_t>(stream), e);
-    return rc ? rc : ok();
+    return rc ? rc : srg_ok();
 }
 
 int srg_spmm_cheby_f32(const int64_t* indptr, const int32_t* indices, const float* values,
@@ -2458,21 +2506,21 @@ int srg_spmm_cheby_f32(const int64_t* indptr, const int32_t* indices, const floa
     SRG_DEVICE_GUARD(stream);
     int rc = check_spmm_args(indptr, indices, values, n_rows, Tc, ldc, Tn, ldn, d);
     if (rc) return rc;
-    if (mode != SRG_CHEBY_INIT && mode != SRG_CHEBY_STEP) return fail(SRG_ERR_INVALID, "cheby mode %d", mode);
-    if (n_scales < 1 || n_scales > 8) return fail(SRG_ERR_INVALID, "n_scales=%d not in [1,8]", n_scales);
-    if (!coef || (mode == SRG_CHEBY_INIT && !coef_prev)) return fail(SRG_ERR_INVALID, "null coefficient array");
-    if (flags & SRG_SPMM_ACCUMULATE) return fail(SRG_ERR_INVALID, "the Chebyshev epilogue starts every chain from 0");
-    if (n_rows == 0 || d == 0) return ok();
-    if (!R || ldr < d) return fail(SRG_ERR_INVALID, "R=%p ldr=%lld < d=%d", (void*)R, (long long)ldr, d);
-    if (n_scales > 1 && r_stride < n_rows * ldr && r_stride > -n_rows * ldr)
-        return fail(SRG_ERR_INVALID, "r_stride overlaps the scale panels");
-    if (mode == SRG_CHEBY_STEP && (!To || ldo < d))
-        return fail(SRG_ERR_INVALID, "step needs To with ldo >= d (To=%p ldo=%lld)", (const void*)To, (long long)ldo);
-    if (Tn == Tc) return fail(SRG_ERR_INVALID, "Tn must not alias Tc (its rows are gathered)");
-    if (mode == SRG_CHEBY_STEP && To == Tn && ldo != ldn)
-        return fail(SRG_ERR_INVALID, "Tn may alias To only with the same leading dimension");
-    if (R == Tn || R == Tc || (mode == SRG_CHEBY_STEP && R == To)) return fail(SRG_ERR_INVALID, "R must not alias a T panel");
+    if (mode != SRG_CHEBY_INIT && mode != SRG_CHEBY_STEP) return srg_fail(SRG_ERR_INVALID, "cheby mode %d", mode);
     Epi e{};
+    rc = cheby_coefs<float>(mode, coef_prev, coef, n_scales, e.cf);
+    if (rc) return rc;
+    if (flags & SRG_SPMM_ACCUMULATE) return srg_fail(SRG_ERR_INVALID, "the Chebyshev epilogue starts every chain from 0");
+    if (n_rows == 0 || d == 0) return srg_ok();
+    if (!R || ldr < d) return srg_fail(SRG_ERR_INVALID, "R=%p ldr=%lld < d=%d", (void*)R, (long long)ldr, d);
+    if (n_scales > 1 && r_stride < n_rows * ldr && r_stride > -n_rows * ldr)
+        return srg_fail(SRG_ERR_INVALID, "r_stride overlaps the scale panels");
+    if (mode == SRG_CHEBY_STEP && (!To || ldo < d))
+        return srg_fail(SRG_ERR_INVALID, "step needs To with ldo >= d (To=%p ldo=%lld)", (const void*)To, (long long)ldo);
+    if (Tn == Tc) return srg_fail(SRG_ERR_INVALID, "Tn must not alias Tc (its rows are gathered)");
+    if (mode == SRG_CHEBY_STEP && To == Tn && ldo != ldn)
+        return srg_fail(SRG_ERR_INVALID, "Tn may alias To only with the same leading dimension");
+    if (R == Tn || R == Tc || (mode == SRG_CHEBY_STEP && R == To)) return srg_fail(SRG_ERR_INVALID, "R must not alias a T panel");
     e.cto = mode == SRG_CHEBY_STEP ? To : nullptr;
     e.ldo = mode == SRG_CHEBY_STEP ? ldo : 0;
     e.R = R;
@@ -2482,13 +2530,9 @@ int srg_spmm_cheby_f32(const int64_t* indptr, const int32_t* indices, const floa
     e.ns = n_scales;
     e.a1 = a1;
     e.a2 = a2;
-    for (int i = 0; i < 8; ++i) {
-        e.cf.prev[i] = (mode == SRG_CHEBY_INIT && i < n_scales) ? 0.5f * coef_prev[i] : 0.0f;
-        e.cf.cur[i] = i < n_scales ? coef[i] : 0.0f;
-    }
     rc = launch_spmm<int64_t, kEpiCheby>(indptr, indices, values, n_rows, row_order, n_hub, n_heavy, Tc, ldc, Tn, ldn,
                                          d, flags, static_cast<hipStream_t>(stream), e);
-    return rc ? rc : ok();
+    return rc ? rc : srg_ok();
 }
 
 int srg_propagate_khop_f32(const int64_t* indptr, const int32_t* indices, const float* values,
@@ -2497,10 +2541,10 @@ int srg_propagate_khop_f32(const int64_t* indptr, const int32_t* indices, const 
                            int64_t ld, int32_t d, int32_t K, uint32_t flags, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (K < 0) return fail(SRG_ERR_INVALID, "K=%d < 0", K);
-    if (K > 0 && !panels) return fail(SRG_ERR_INVALID, "null panels");
+    if (K < 0) return srg_fail(SRG_ERR_INVALID, "K=%d < 0", K);
+    if (K > 0 && !panels) return srg_fail(SRG_ERR_INVALID, "null panels");
     for (int k = 0; k <= K; ++k)
-        if (!panels[k] && n_rows > 0 && d > 0) return fail(SRG_ERR_INVALID, "panels[%d] is null", k);
+        if (!panels[k] && n_rows > 0 && d > 0) return srg_fail(SRG_ERR_INVALID, "panels[%d] is null", k);
     int rc = check_spmm_args(indptr, indices, values, n_rows, panels ? panels[0] : nullptr, ld,
                              panels ? panels[0] : nullptr, ld, d);
     if (rc) return rc;
@@ -2523,7 +2567,7 @@ int srg_propagate_khop_f32(const int64_t* indptr, const int32_t* indices, const 
                                   panels[k], ld, d, f, static_cast<hipStream_t>(stream));
         if (rc) return rc;
     }
-    return ok();
+    return srg_ok();
 }
 
 // one hop of a launch list: X (ldx) -> Y (ldy); launch i carries the aggregation epilogue (agg = (init ?
@@ -2535,13 +2579,7 @@ static int run_hop_launches(const srg_hop_launch* launches, int32_t n_launch, bo
 {
     for (int i = 0; i < n_launch; ++i) {
         const srg_hop_launch& L = launches[i];
-        Epi e{};
-        if (agg && agg_on && agg_on[i]) {
-            e.agg = agg;
-            e.lda = lda;
-            e.w = w;
-            e.init = agg_init ? 1 : 0;
-        }
+        Epi e = (agg && agg_on && agg_on[i]) ? agg_epi(agg, lda, w, agg_init) : Epi{};
         int rc;
         if (L.row_end) {
             e.row_end = L.row_end;
@@ -2556,15 +2594,7 @@ static int run_hop_launches(const srg_hop_launch* launches, int32_t n_launch, bo
         }
         if (rc) return rc;
     }
-    if (join_hub) {
-        std::lock_guard<std::mutex> lock(g_side_mu);
-        auto it = g_side.find(std::make_pair(dev, s));
-        if (it != g_side.end() && it->second.pending) {
-            SRG_HIP_CHECK(hipStreamWaitEvent(s, it->second.join, 0));
-            it->second.pending = false;
-        }
-    }
-    return SRG_OK;
+    return join_hub ? join_side_stream(dev, s, true) : SRG_OK;
 }
 
 static int check_launches(const srg_hop_launch* launches, int32_t n_launch, const float* X, int64_t ldx,
@@ -2575,9 +2605,9 @@ static int check_launches(const srg_hop_launch* launches, int32_t n_launch, cons
         int rc = check_spmm_args(L.row_beg, L.indices, L.values, L.n_rows, X, ldx, Y, ldy, d);
         if (rc) return rc;
         if (L.n_rows > 0 && L.n_hub + L.n_heavy > 0 && !L.row_order)
-            return fail(SRG_ERR_INVALID, "launch %d: hub / heavy rows need a row_order", i);
+            return srg_fail(SRG_ERR_INVALID, "launch %d: hub / heavy rows need a row_order", i);
         if ((L.slot_beg != nullptr) != (L.slot_end != nullptr) || (L.slot_beg && !L.row_end))
-            return fail(SRG_ERR_INVALID, "launch %d: slot_beg / slot_end come together, with row_end", i);
+            return srg_fail(SRG_ERR_INVALID, "launch %d: slot_beg / slot_end come together, with row_end", i);
     }
     return SRG_OK;
 }
@@ -2586,11 +2616,11 @@ int srg_propagate_plan_f32(const srg_hop_launch* launches, int32_t n_launch, int
                            float* const* panels, int64_t ld, int32_t d, int32_t K, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (K < 0 || n_launch < 0) return fail(SRG_ERR_INVALID, "K=%d / n_launch=%d < 0", K, n_launch);
-    if (K == 0 || n_launch == 0) return ok();
-    if (!launches || !panels) return fail(SRG_ERR_INVALID, "null launches or panels");
+    if (K < 0 || n_launch < 0) return srg_fail(SRG_ERR_INVALID, "K=%d / n_launch=%d < 0", K, n_launch);
+    if (K == 0 || n_launch == 0) return srg_ok();
+    if (!launches || !panels) return srg_fail(SRG_ERR_INVALID, "null launches or panels");
     for (int k = 0; k <= K; ++k)
-        if (!panels[k] && d > 0) return fail(SRG_ERR_INVALID, "panels[%d] is null", k);
+        if (!panels[k] && d > 0) return srg_fail(SRG_ERR_INVALID, "panels[%d] is null", k);
     int rc = check_launches(launches, n_launch, panels[0], ld, panels[0], ld, d);
     if (rc) return rc;
     for (int i = 0; i < n_launch; ++i) {
@@ -2598,7 +2628,7 @@ int srg_propagate_plan_f32(const srg_hop_launch* launches, int32_t n_launch, int
         // k+1's launches on `stream` read panels[k]: a data race
         const srg_hop_launch& L = launches[i];
         if (!join_hub && K > 1 && L.n_hub > 0 && (L.flags & SRG_SPMM_HUB_NOJOIN))
-            return fail(SRG_ERR_INVALID, "launch %d: HUB_NOJOIN hub rows over K=%d hops need join_hub", i, K);
+            return srg_fail(SRG_ERR_INVALID, "launch %d: HUB_NOJOIN hub rows over K=%d hops need join_hub", i, K);
     }
     const hipStream_t s = static_cast<hipStream_t>(stream);
     for (int k = 1; k <= K; ++k) {
@@ -2606,7 +2636,7 @@ int srg_propagate_plan_f32(const srg_hop_launch* launches, int32_t n_launch, int
                               0, 0.0f, 0, s, guard_.dev);
         if (rc) return rc;
     }
-    return ok();
+    return srg_ok();
 }
 
 // srg_plan.hip's single hop (srg_plan_hop_f32): the launches of one hop between panels of their own
@@ -2617,15 +2647,15 @@ __attribute__((visibility("hidden"))) int srg_run_plan_hop(const srg_hop_launch*
                                                            int64_t lda, float w, int32_t agg_init, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (n_launch <= 0) return ok();
+    if (n_launch <= 0) return srg_ok();
     int rc = check_launches(launches, n_launch, X, ldx, Y, ldy, d);
     if (rc) return rc;
-    if (X == Y) return fail(SRG_ERR_INVALID, "Y must not alias X (its rows are gathered)");
+    if (X == Y) return srg_fail(SRG_ERR_INVALID, "Y must not alias X (its rows are gathered)");
     if (agg && (lda < d || agg == Y || agg == X))
-        return fail(SRG_ERR_INVALID, "aggregation panel: lda=%lld < d=%d or agg aliases X / Y", (long long)lda, d);
+        return srg_fail(SRG_ERR_INVALID, "aggregation panel: lda=%lld < d=%d or agg aliases X / Y", (long long)lda, d);
     rc = run_hop_launches(launches, n_launch, join_hub != 0, X, ldx, Y, ldy, d, agg_on, agg, lda, w, agg_init,
                           static_cast<hipStream_t>(stream), guard_.dev);
-    return rc ? rc : ok();
+    return rc ? rc : srg_ok();
 }
 
 int srg_cheby_step_f64(const int64_t* indptr, const int32_t* indices, const double* values,
@@ -2634,7 +2664,7 @@ int srg_cheby_step_f64(const int64_t* indptr, const int32_t* indices, const doub
                        double a2, const double* coef_prev, const double* coef, int32_t n_scales,
                        double* R, int64_t r_stride, void* stream)
 {
-    if (mode & SRG_CHEBY_HUB_NOJOIN) return fail(SRG_ERR_INVALID, "cheby mode %d: HUB_NOJOIN needs the hub entry", mode);
+    if (mode & SRG_CHEBY_HUB_NOJOIN) return srg_fail(SRG_ERR_INVALID, "cheby mode %d: HUB_NOJOIN needs the hub entry", mode);
     SRG_DEVICE_GUARD(stream);
     return launch_cheby<double>(indptr, indices, values, n_rows, row_order, Tc, To, Tn, ld, d, mode,
                                 a1, a2, coef_prev, coef, n_scales, R, r_stride,
@@ -2668,7 +2698,7 @@ __attribute__((visibility("hidden"))) int srg_run_plan_cheby_f64(const srg_hop_l
     ChebyCoef<double> cf;
     int rc0 = cheby_setup<double>(mode, coef_prev, coef, n_scales, To, cf);
     if (rc0) return rc0;
-    if (d < 0 || ld < d) return fail(SRG_ERR_INVALID, "d=%d, ld=%lld", d, (long long)ld);
+    if (d < 0 || ld < d) return srg_fail(SRG_ERR_INVALID, "d=%d, ld=%lld", d, (long long)ld);
     if (n_launch == 1 && !launches[0].slot_beg) {
         const srg_hop_launch& L = launches[0];
         return launch_cheby<double>(indptr, indices, values, L.n_rows, L.row_order, Tc, To, Tn, ld, d, mode, a1, a2,
@@ -2678,34 +2708,28 @@ __attribute__((visibility("hidden"))) int srg_run_plan_cheby_f64(const srg_hop_l
     for (int i = 0; i < n_launch; ++i) {
         const srg_hop_launch& L = launches[i];
         if (!L.slot_beg || !L.slot_end || (L.n_rows > 0 && !L.row_order))
-            return fail(SRG_ERR_INVALID, "launch %d: a blocked fp64 step reads spans by slot", i);
+            return srg_fail(SRG_ERR_INVALID, "launch %d: a blocked fp64 step reads spans by slot", i);
         if (roles[i] & (SRG_CHEBY64_LAST | SRG_CHEBY64_HUBS)) n_total += L.n_rows;
     }
-    if (d == 0 || n_total == 0) return ok();
-    if (!Tc || !Tn || !R || !indices || !values) return fail(SRG_ERR_INVALID, "null panel or entry array");
-    if (r_stride < n_total * ld && n_scales > 1) return fail(SRG_ERR_INVALID, "r_stride too small for stacked scale panels");
+    if (d == 0 || n_total == 0) return srg_ok();
+    if (!Tc || !Tn || !R || !indices || !values) return srg_fail(SRG_ERR_INVALID, "null panel or entry array");
+    if (r_stride < n_total * ld && n_scales > 1) return srg_fail(SRG_ERR_INVALID, "r_stride too small for stacked scale panels");
     const bool v2 = d % 2 == 0 && ld % 2 == 0 && aligned(Tc, 16) && aligned(Tn, 16) && aligned(R, 16) &&
                     r_stride % 2 == 0 && (To == nullptr || aligned(To, 16));
     const int n_slices = (d + kHub64Cols - 1) / kHub64Cols;
-    SideStream* ss = nullptr;
-    std::unique_lock<std::mutex> side_lock(g_side_mu, std::defer_lock);
+    HubFork hub(s);
     for (int i = 0; i < n_launch; ++i) {
         const srg_hop_launch& L = launches[i];
         if (L.n_rows <= 0) continue;
         int role = roles[i];
         if (role == SRG_CHEBY64_HUBS) {
             if (v2 && L.n_rows * n_slices <= INT32_MAX - 64) {   // fork: the hub workgroups beside the blocks
-                side_lock.lock();
-                int rc = side_stream_locked(s, &ss);
-                if (rc) return rc;
-                SRG_HIP_CHECK(hipEventRecord(ss->fork, s));
-                SRG_HIP_CHECK(hipStreamWaitEvent(ss->stream, ss->fork, 0));
-                launch_hub64(L.n_rows * n_slices, ss->stream, indptr, indices, values, L.row_order, n_slices, Tc, To,
+                if (int rc = hub.fork()) return rc;
+                launch_hub64(L.n_rows * n_slices, hub.stream(), indptr, indices, values, L.row_order, n_slices, Tc, To,
                              Tn, ld, d, mode, a1, a2, cf, n_scales, R, r_stride);
                 SRG_HIP_CHECK(hipGetLastError());
-                SRG_HIP_CHECK(hipEventRecord(ss->join, ss->stream));
-                hipLaunchKernelGGL(k_dispatch_delay, dim3(1), dim3(64), 0, s, kHubDelayUs);
-                SRG_HIP_CHECK(hipGetLastError());
+                if (int rc = hub.record_join(false)) return rc;   // joined below, before the step returns
+                if (int rc = hub.delay()) return rc;
                 continue;
             }
             role = SRG_CHEBY64_FIRST | SRG_CHEBY64_LAST;   // row waves over their whole spans
@@ -2735,8 +2759,8 @@ __attribute__((visibility("hidden"))) int srg_run_plan_cheby_f64(const srg_hop_l
             SRG_HIP_CHECK(hipGetLastError());
         }
     }
-    if (ss) SRG_HIP_CHECK(hipStreamWaitEvent(s, ss->join, 0));   // join
-    return ok();
+    if (int rc = hub.join()) return rc;
+    return srg_ok();
 }
 
 int srg_cheby_step_f32(const int64_t* indptr, const int32_t* indices, const float* values,
@@ -2757,34 +2781,25 @@ int srg_cheby_epilogue_f32(float* Tn, int64_t ldn, const float* Tc, int64_t ldc,
                            int64_t ldr, int64_t r_stride, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
+    ChebyCoef<float> cf;
+    int rc = cheby_coefs<float>(mode, coef_prev, coef, n_scales, cf);
+    if (rc) return rc;
     const int m = mode & ~SRG_CHEBY_NO_T;
-    if (m != SRG_CHEBY_INIT && m != SRG_CHEBY_STEP && m != SRG_CHEBY_INIT_T && m != SRG_CHEBY_STEP_FIRST)
-        return fail(SRG_ERR_INVALID, "cheby mode %d", mode);
     const bool init = m == SRG_CHEBY_INIT || m == SRG_CHEBY_INIT_T;
     const bool needs_r = m != SRG_CHEBY_INIT_T;
-    if (n_scales < 1 || n_scales > 8) return fail(SRG_ERR_INVALID, "n_scales=%d not in [1,8]", n_scales);
-    if ((needs_r && !coef) || ((m == SRG_CHEBY_INIT || m == SRG_CHEBY_STEP_FIRST) && !coef_prev))
-        return fail(SRG_ERR_INVALID, "null coefficient array");
     if (n_rows < 0 || d < 0 || ldn < d || (needs_r && ldr < d) || (init ? ldc < d : ldo < d) ||
         (m == SRG_CHEBY_STEP_FIRST && ldc < d))
-        return fail(SRG_ERR_INVALID, "bad shape n_rows=%lld d=%d", (long long)n_rows, d);
+        return srg_fail(SRG_ERR_INVALID, "bad shape n_rows=%lld d=%d", (long long)n_rows, d);
     if (needs_r && n_scales > 1 && r_stride < n_rows * ldr && r_stride > -n_rows * ldr)
-        return fail(SRG_ERR_INVALID, "r_stride overlaps the scale panels");
-    if (n_rows == 0 || d == 0) return ok();
+        return srg_fail(SRG_ERR_INVALID, "r_stride overlaps the scale panels");
+    if (n_rows == 0 || d == 0) return srg_ok();
     if (!Tn || (needs_r && !R) || (init ? !Tc : !To) || (m == SRG_CHEBY_STEP_FIRST && !Tc))
-        return fail(SRG_ERR_INVALID, "null panel");
-    ChebyCoef<float> cf;
-    for (int i = 0; i < 8; ++i) {
-        const bool on = i < n_scales;
-        cf.prev[i] = ((m == SRG_CHEBY_INIT || m == SRG_CHEBY_STEP_FIRST) && on) ? 0.5f * coef_prev[i] : 0.0f;
-        cf.mid[i] = (m == SRG_CHEBY_STEP_FIRST && on) ? coef_prev[n_scales + i] : 0.0f;
-        cf.cur[i] = (needs_r && on) ? coef[i] : 0.0f;
-    }
+        return srg_fail(SRG_ERR_INVALID, "null panel");
     const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 256 * 16);
     hipLaunchKernelGGL(k_cheby_epilogue, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        Tn, ldn, Tc, ldc, To, ldo, n_rows, d, mode, a1, a2, cf, n_scales, R, ldr, r_stride);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_hop_accumulate_f32(float* agg, int64_t lda, const float* y, int64_t ldy, int64_t n_rows,
@@ -2792,17 +2807,17 @@ int srg_hop_accumulate_f32(float* agg, int64_t lda, const float* y, int64_t ldy,
 {
     SRG_DEVICE_GUARD(stream);
     if (mode != SRG_ACC_INIT && mode != SRG_ACC_ADD && mode != SRG_ACC_DIV)
-        return fail(SRG_ERR_INVALID, "accumulate mode %d", mode);
+        return srg_fail(SRG_ERR_INVALID, "accumulate mode %d", mode);
     if (n_rows < 0 || d < 0 || lda < d || (mode != SRG_ACC_DIV && ldy < d))
-        return fail(SRG_ERR_INVALID, "bad shape n_rows=%lld d=%d lda=%lld ldy=%lld", (long long)n_rows, d,
-                    (long long)lda, (long long)ldy);
-    if (n_rows == 0 || d == 0) return ok();
-    if (!agg || (mode != SRG_ACC_DIV && !y)) return fail(SRG_ERR_INVALID, "null pointer");
+        return srg_fail(SRG_ERR_INVALID, "bad shape n_rows=%lld d=%d lda=%lld ldy=%lld", (long long)n_rows, d,
+                        (long long)lda, (long long)ldy);
+    if (n_rows == 0 || d == 0) return srg_ok();
+    if (!agg || (mode != SRG_ACC_DIV && !y)) return srg_fail(SRG_ERR_INVALID, "null pointer");
     const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 256 * 16);
     hipLaunchKernelGGL(k_hop_accumulate, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        agg, lda, y, ldy, n_rows, d, w, mode);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_tail_record_f32(float* hist, const float* y, int64_t ldy, int32_t d, int64_t flat_start,
@@ -2810,14 +2825,14 @@ int srg_tail_record_f32(float* hist, const float* y, int64_t ldy, int32_t d, int
 {
     SRG_DEVICE_GUARD(stream);
     if (d <= 0 || ldy < d || flat_start < 0 || len < 0 || len > SRG_TAIL_MAX)
-        return fail(SRG_ERR_INVALID, "bad tail d=%d ldy=%lld flat_start=%lld len=%d", d, (long long)ldy,
-                    (long long)flat_start, len);
-    if (len == 0) return ok();
-    if (!hist || !y) return fail(SRG_ERR_INVALID, "null pointer");
+        return srg_fail(SRG_ERR_INVALID, "bad tail d=%d ldy=%lld flat_start=%lld len=%d", d, (long long)ldy,
+                        (long long)flat_start, len);
+    if (len == 0) return srg_ok();
+    if (!hist || !y) return srg_fail(SRG_ERR_INVALID, "null pointer");
     hipLaunchKernelGGL(k_tail_record, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
                        hist, y, ldy, d, flat_start, len, w);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_tail_rowsum_f32(float* agg, int64_t lda, int32_t d, int64_t flat_start, int32_t len,
@@ -2825,14 +2840,14 @@ int srg_tail_rowsum_f32(float* agg, int64_t lda, int32_t d, int64_t flat_start, 
 {
     SRG_DEVICE_GUARD(stream);
     if (d <= 0 || lda < d || flat_start < 0 || len < 0 || len > SRG_TAIL_MAX || n_terms < 0)
-        return fail(SRG_ERR_INVALID, "bad tail d=%d lda=%lld flat_start=%lld len=%d n_terms=%d", d,
-                    (long long)lda, (long long)flat_start, len, n_terms);
-    if (len == 0) return ok();
-    if (!agg || (n_terms > 0 && !hist)) return fail(SRG_ERR_INVALID, "null pointer");
+        return srg_fail(SRG_ERR_INVALID, "bad tail d=%d lda=%lld flat_start=%lld len=%d n_terms=%d", d,
+                        (long long)lda, (long long)flat_start, len, n_terms);
+    if (len == 0) return srg_ok();
+    if (!agg || (n_terms > 0 && !hist)) return srg_fail(SRG_ERR_INVALID, "null pointer");
     hipLaunchKernelGGL(k_tail_rowsum, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
                        agg, lda, d, flat_start, len, hist, n_terms);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_gather_rows_f32(const float* src, int64_t lds, int64_t n_src, const int64_t* idx, int64_t n_idx,
@@ -2840,10 +2855,10 @@ int srg_gather_rows_f32(const float* src, int64_t lds, int64_t n_src, const int6
 {
     SRG_DEVICE_GUARD(stream);
     if (n_idx < 0 || n_src < 0 || d < 0 || (d > 0 && (lds < d || ldd < d)))
-        return fail(SRG_ERR_INVALID, "bad gather shape n_idx=%lld n_src=%lld d=%d lds=%lld ldd=%lld",
-                    (long long)n_idx, (long long)n_src, d, (long long)lds, (long long)ldd);
-    if (n_idx == 0 || d == 0) return ok();
-    if (!src || !idx || !dst) return fail(SRG_ERR_INVALID, "null pointer");
+        return srg_fail(SRG_ERR_INVALID, "bad gather shape n_idx=%lld n_src=%lld d=%d lds=%lld ldd=%lld",
+                        (long long)n_idx, (long long)n_src, d, (long long)lds, (long long)ldd);
+    if (n_idx == 0 || d == 0) return srg_ok();
+    if (!src || !idx || !dst) return srg_fail(SRG_ERR_INVALID, "null pointer");
     const int vec = pick_vec(d, lds, ldd, src, dst, sizeof(float));
     const int cpr = d / vec;
     const int S = cpr >= 64 ? 64 : cpr > 16 ? 32 : cpr > 8 ? 16 : cpr > 4 ? 8 : 4;
@@ -2868,7 +2883,7 @@ int srg_gather_rows_f32(const float* src, int64_t lds, int64_t n_src, const int6
 #undef SRG_GATHER_S
 #undef SRG_GATHER
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_hub_side_streams(void)
@@ -2880,13 +2895,8 @@ int srg_hub_side_streams(void)
 int srg_hub_join(void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    auto it = g_side.find(std::make_pair(guard_.dev, static_cast<hipStream_t>(stream)));
-    if (it != g_side.end() && it->second.join) {
-        SRG_HIP_CHECK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), it->second.join, 0));
-        it->second.pending = false;
-    }
-    return ok();
+    const int rc = join_side_stream(guard_.dev, static_cast<hipStream_t>(stream), false);
+    return rc ? rc : srg_ok();
 }
 
 }  // extern "C"
@@ -2896,14 +2906,14 @@ template <typename T>
 int launch_segment_sum(const int64_t* seg_ptr, const T* vals, int64_t n_seg, T* out, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (n_seg < 0) return fail(SRG_ERR_INVALID, "n_seg=%lld < 0", (long long)n_seg);
-    if (n_seg == 0) return ok();
-    if (!seg_ptr || !out) return fail(SRG_ERR_INVALID, "null pointer");
+    if (n_seg < 0) return srg_fail(SRG_ERR_INVALID, "n_seg=%lld < 0", (long long)n_seg);
+    if (n_seg == 0) return srg_ok();
+    if (!seg_ptr || !out) return srg_fail(SRG_ERR_INVALID, "null pointer");
     const unsigned blocks = (unsigned)std::min<int64_t>((n_seg + 255) / 256, 1 << 16);   // 64 segments per wave
     hipLaunchKernelGGL(k_segment_sum<T>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        seg_ptr, vals, n_seg, out);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 }  // namespace
 
@@ -2925,22 +2935,22 @@ int srg_spmm_csr_f64(const int64_t* indptr, const int32_t* indices, const double
     SRG_DEVICE_GUARD(stream);
     int rc = check_spmm_args(indptr, indices, values, n_rows, X, ldx, Y, ldy, d);
     if (rc) return rc;
-    if (n_rows == 0 || d == 0) return ok();
+    if (n_rows == 0 || d == 0) return srg_ok();
     const int64_t total = n_rows * (int64_t)d;
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20);
     hipLaunchKernelGGL(k_spmm_f64, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        indptr, indices, values, n_rows, X, ldx, Y, ldy, d);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_csr_validate(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
                      int64_t n_cols, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (n_rows < 0 || nnz < 0 || n_cols < 0) return fail(SRG_ERR_INVALID, "negative size");
-    if (!indptr) return fail(SRG_ERR_INVALID, "null indptr");
-    if (nnz > 0 && !indices) return fail(SRG_ERR_INVALID, "null indices");
+    if (n_rows < 0 || nnz < 0 || n_cols < 0) return srg_fail(SRG_ERR_INVALID, "negative size");
+    if (!indptr) return srg_fail(SRG_ERR_INVALID, "null indptr");
+    if (nnz > 0 && !indices) return srg_fail(SRG_ERR_INVALID, "null indices");
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned int* d_bad = nullptr;
     SRG_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&d_bad), sizeof(unsigned int), s));
@@ -2953,27 +2963,27 @@ int srg_csr_validate(const int64_t* indptr, const int32_t* indices, int64_t n_ro
     SRG_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
     SRG_HIP_CHECK(hipFreeAsync(d_bad, s));
     SRG_HIP_CHECK(hipStreamSynchronize(s));
-    if (bad & 1u) return fail(SRG_ERR_INVALID, "column id outside [0, %lld)", (long long)n_cols);
-    if (bad & 2u) return fail(SRG_ERR_INVALID, "indptr decreases");
-    if (bad & 4u) return fail(SRG_ERR_INVALID, "indptr[0] != 0");
-    if (bad & 8u) return fail(SRG_ERR_INVALID, "indptr[n_rows] != nnz=%lld", (long long)nnz);
-    return ok();
+    if (bad & 1u) return srg_fail(SRG_ERR_INVALID, "column id outside [0, %lld)", (long long)n_cols);
+    if (bad & 2u) return srg_fail(SRG_ERR_INVALID, "indptr decreases");
+    if (bad & 4u) return srg_fail(SRG_ERR_INVALID, "indptr[0] != 0");
+    if (bad & 8u) return srg_fail(SRG_ERR_INVALID, "indptr[n_rows] != nnz=%lld", (long long)nnz);
+    return srg_ok();
 }
 
 int srg_csr_col_splits(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
                        int32_t n_blocks, int64_t* splits, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (n_rows < 0 || n_cols < 0) return fail(SRG_ERR_INVALID, "negative size");
-    if (n_blocks < 2 || n_blocks > 64) return fail(SRG_ERR_INVALID, "n_blocks=%d not in [2, 64]", n_blocks);
+    if (n_rows < 0 || n_cols < 0) return srg_fail(SRG_ERR_INVALID, "negative size");
+    if (n_blocks < 2 || n_blocks > 64) return srg_fail(SRG_ERR_INVALID, "n_blocks=%d not in [2, 64]", n_blocks);
     const int64_t work = n_rows * (n_blocks - 1);
-    if (work == 0) return ok();
-    if (!indptr || !splits) return fail(SRG_ERR_INVALID, "null indptr or splits");
-    if ((work + 255) / 256 > INT32_MAX) return fail(SRG_ERR_INVALID, "grid too large");
+    if (work == 0) return srg_ok();
+    if (!indptr || !splits) return srg_fail(SRG_ERR_INVALID, "null indptr or splits");
+    if ((work + 255) / 256 > INT32_MAX) return srg_fail(SRG_ERR_INVALID, "grid too large");
     hipLaunchKernelGGL(k_col_splits, dim3((unsigned)((work + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), indptr, indices, n_rows, n_cols, (int)n_blocks, splits);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_csr_copy_spans(const int32_t* order, int64_t n_order, const int64_t* beg, const int64_t* end,
@@ -2981,40 +2991,35 @@ int srg_csr_copy_spans(const int32_t* order, int64_t n_order, const int64_t* beg
                        float* out_values, int64_t* out_beg, int64_t* out_end, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (n_order < 0) return fail(SRG_ERR_INVALID, "n_order=%lld < 0", (long long)n_order);
-    if (n_order == 0) return ok();
+    if (n_order < 0) return srg_fail(SRG_ERR_INVALID, "n_order=%lld < 0", (long long)n_order);
+    if (n_order == 0) return srg_ok();
     if (!order || !beg || !end || !pos || !out_beg || !out_end)
-        return fail(SRG_ERR_INVALID, "null order / span / position array");
+        return srg_fail(SRG_ERR_INVALID, "null order / span / position array");
     const int64_t rows_per_block = 256 / 16;
     const unsigned blocks = (unsigned)std::min<int64_t>((n_order + rows_per_block - 1) / rows_per_block, 1 << 20);
     hipLaunchKernelGGL(k_copy_spans, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), order, n_order,
                        beg, end, indices, values, pos, out_indices, out_values, out_beg, out_end);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 int srg_csr_mirror(const int64_t* indptr, const int32_t* indices, const int64_t* rows, int64_t n_rows,
                    int64_t nnz, int64_t* mirror, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (n_rows < 0 || nnz < 0) return fail(SRG_ERR_INVALID, "negative size");
-    if (nnz == 0) return ok();
-    if (!indptr || !indices || !rows || !mirror) return fail(SRG_ERR_INVALID, "null pointer");
+    if (n_rows < 0 || nnz < 0) return srg_fail(SRG_ERR_INVALID, "negative size");
+    if (nnz == 0) return srg_ok();
+    if (!indptr || !indices || !rows || !mirror) return srg_fail(SRG_ERR_INVALID, "null pointer");
     const unsigned blocks = (unsigned)std::min<int64_t>((nnz + 255) / 256, 1 << 20);
     hipLaunchKernelGGL(k_csr_mirror, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), indptr, indices,
                        rows, nnz, mirror);
     SRG_HIP_CHECK(hipGetLastError());
-    return ok();
+    return srg_ok();
 }
 
 const char* srg_last_error(void) { return g_err_msg; }
 int srg_last_error_code(void) { return g_err_code; }
-// the communicator entries (srg_comm.hip) report through the same thread-local status
-__attribute__((visibility("hidden"))) void srg_set_error(int code, const char* msg)
-{
-    (void)fail(code, "%s", msg);
-}
-void srg_clear_error(void) { (void)ok(); }
+void srg_clear_error(void) { (void)srg_ok(); }
 const char* srg_version(void) { return "srgnn_hip " SRG_GIT_REV " gfx950"; }
 
 }  // extern "C"

@@ -303,6 +303,30 @@ def call(device, name: str, *args) -> None:
         check(fn(*args), name)
 
 
+class hub_forked:
+    """A hub group forked onto the library's hub side stream of `device`'s current stream: the block
+    launches the hub rows unjoined (HUB_NOJOIN) and whatever runs beside them; leaving it, normally or
+    by an exception, joins the side stream into the current stream (srg_hub_join), so hub rows are
+    never left running unjoined.  join() joins early; leaving the block is then a no-op.  on=False:
+    the caller forked nothing, and nothing is joined."""
+
+    def __init__(self, device, on: bool = True):
+        self.device = device
+        self._open = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def join(self) -> None:
+        if self._open:
+            self._open = False
+            call(self.device, "srg_hub_join", stream(self.device))
+
+    def __exit__(self, *exc):
+        self.join()
+        return False
+
+
 def call_host(name: str, *args) -> None:
     """Entry points that choose their devices themselves (srg_comm_*, srg_dist_propagate_khop_f32:
     every shard names its device) -- no device guard; raises SrgError on a failed status."""

@@ -550,21 +550,20 @@ class HaloPartitionedOperator:
             return
         from . import _lib
         fork = bool(self.views[C][1] and self.views[C][3] and self._hip)
-        if self.views[C][1]:
-            if fork:
-                self._hub_launch(src, out)
-            else:
-                self._spmm(self._A[C], src, out)
-        blocks = self.chunk_blocks(src.shape[1])
-        for c in range(C):
-            if self.views[c][1]:
-                self._chunk_spmm(c, src, out, blocks)
-            if after_group is not None:
-                after_group(c)
-        if ghosts and self.n_ghost:
-            self._spmm(gA, src, dst)
-        if fork:
-            _lib.call(self.device, "srg_hub_join", _lib.stream(self.device))
+        with _lib.hub_forked(self.device, fork):
+            if self.views[C][1]:
+                if fork:
+                    self._hub_launch(src, out)
+                else:
+                    self._spmm(self._A[C], src, out)
+            blocks = self.chunk_blocks(src.shape[1])
+            for c in range(C):
+                if self.views[c][1]:
+                    self._chunk_spmm(c, src, out, blocks)
+                if after_group is not None:
+                    after_group(c)
+            if ghosts and self.n_ghost:
+                self._spmm(gA, src, dst)
         if after_group is not None:
             after_group(C)
 
@@ -606,23 +605,24 @@ class HaloPartitionedOperator:
         out = dst[: self.rows]
         C = self.C
         fork = bool(self.views[C][1] and self.views[C][3])
-        if self.views[C][1]:
-            if fork:
-                self._hub_launch(src, out)
-            else:
-                self._spmm(self._A[C], src, out)
         pending = []
-        blocks = self.chunk_blocks(src.shape[1])
-        for c in range(C):
-            if self.views[c][1]:
-                self._chunk_spmm(c, src, out, blocks)
-            if c == 0 and fork:
-                _lib.call(self.device, "srg_hub_join", _lib.stream(self.device))
-            a, b = self.chunk_ranges[c]
-            if b > a:
-                epilogue(a, b)
-            pending.append(self._exchange_group(dst, c, async_op=True))
-        pending.append(self._exchange_group(dst, C, async_op=True))
+        with _lib.hub_forked(self.device, fork) as hub:
+            if self.views[C][1]:
+                if fork:
+                    self._hub_launch(src, out)
+                else:
+                    self._spmm(self._A[C], src, out)
+            blocks = self.chunk_blocks(src.shape[1])
+            for c in range(C):
+                if self.views[c][1]:
+                    self._chunk_spmm(c, src, out, blocks)
+                if c == 0:
+                    hub.join()
+                a, b = self.chunk_ranges[c]
+                if b > a:
+                    epilogue(a, b)
+                pending.append(self._exchange_group(dst, c, async_op=True))
+            pending.append(self._exchange_group(dst, C, async_op=True))
         for item in pending:
             if item is not None:
                 item[0].wait()
@@ -872,12 +872,12 @@ class HaloWaveletFilter:
         op = self.opL
         pending = []
         (gh, hub_sched), chunks = self._sched64_groups[0], self._sched64_groups[1:]
-        self._order64(which, Tc, To, Tn, mode | _lib.SRG_CHEBY_HUB_NOJOIN, coef_prev, coef, R, sched=hub_sched)
-        for g, sched in chunks:
-            self._order64(which, Tc, To, Tn, mode, coef_prev, coef, R, sched=sched)
-            if exchange:
-                pending.append(op._exchange_group(Tn, g, async_op=True))
-        _lib.call(op.device, "srg_hub_join", _lib.stream(op.device))
+        with _lib.hub_forked(op.device):
+            self._order64(which, Tc, To, Tn, mode | _lib.SRG_CHEBY_HUB_NOJOIN, coef_prev, coef, R, sched=hub_sched)
+            for g, sched in chunks:
+                self._order64(which, Tc, To, Tn, mode, coef_prev, coef, R, sched=sched)
+                if exchange:
+                    pending.append(op._exchange_group(Tn, g, async_op=True))
         if exchange:
             pending.append(op._exchange_group(Tn, gh, async_op=True))
         for item in pending:

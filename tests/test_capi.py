@@ -133,6 +133,33 @@ def test_planner_rejects_bad_arguments_before_the_device():
     assert L.srg_plan_destroy(None, None) == 0
 
 
+def test_every_source_file_reports_through_the_one_error_state():
+    """One argument check (before any device call) per source file of the library -- spmm, plan, halo, comm,
+    spgemm: each returns its code and leaves its message in the calling thread's srg_last_error, and the next
+    successful call clears it."""
+    L = _lib.lib()
+    out = ctypes.c_void_p()
+    ip = (ctypes.c_int64 * 3)(0, 1, 2)
+    ix = (ctypes.c_int32 * 2)(0, 1)
+    A = _lib.SRG_PLAN_AUTO
+    cases = [
+        ("spmm", lambda: L.srg_spmm_csr_f32(None, None, None, 4, None, 0, 0, None, 2, None, 8, 8, 0, None), "ldx=2"),
+        ("plan", lambda: L.srg_plan_build(ip, None, None, 2, 8, 4, 65, A, A, 0, None, ctypes.byref(out)),
+         "col_blocks=65"),
+        ("halo", lambda: L.srg_halo_plan_build(ip, ix, 2, 2, 5, 1, -1, -1, 0, 0.0, ctypes.byref(out)), "rank 5 of 2"),
+        ("comm", lambda: L.srg_comm_init_loopback(0, 0, ctypes.byref(out)), "nranks=0"),
+        ("spgemm", lambda: L.srg_spgemm_f32(2, None, None, None, 0, None, None, None, 0, None, None, None, None, None,
+                                            0, 0, None), "phase 2"),
+    ]
+    for name, bad, msg in cases:
+        assert bad() == _lib.SRG_ERR_INVALID, name
+        assert L.srg_last_error_code() == _lib.SRG_ERR_INVALID, name
+        assert _lib.last_error() and msg in _lib.last_error(), (name, _lib.last_error())
+        # an empty problem: a successful call that needs no device
+        assert L.srg_spmm_csr_f32(None, None, None, 0, None, 0, 0, None, 8, None, 8, 8, 0, None) == _lib.SRG_OK
+        assert L.srg_last_error_code() == _lib.SRG_OK and _lib.last_error() == "", name
+
+
 @pytest.mark.gpu
 def test_plain_c_host_runs_the_fp64_steps(tmp_path):
     """examples/cheby64_plan.c: a plain C program plans an operator for the fp64 Chebyshev steps (no fp32

@@ -378,3 +378,32 @@ def test_halo_wavelet_f64_group_schedules(world, chunks, hub):
         assert torch.equal(torch.sort(f._sched64.to(torch.int64)).values, torch.arange(f.rows))
         assert f._n_hub64 == (int((deg > t).sum()) if t >= 0 else 0)
         assert f.new_panel(8).dtype == torch.float64 and f.new_panel(8).shape == (f.rows + f.opL.halo, 8)
+
+
+def test_hub_forked_joins_once_even_on_an_exception(monkeypatch):
+    """srgnn._lib.hub_forked (no device, no library: the calls are recorded): leaving the block joins the hub
+    side stream exactly once -- when the block raises (and the exception propagates), after an early join(),
+    and never when nothing was forked."""
+    from srgnn import _lib
+    calls = []
+    monkeypatch.setattr(_lib, "call", lambda device, name, *args: calls.append((device, name, args)))
+    monkeypatch.setattr(_lib, "stream", lambda device: 7)
+    with pytest.raises(KeyError, match="exchange"):
+        with _lib.hub_forked("cuda:0"):
+            raise KeyError("exchange")
+    assert calls == [("cuda:0", "srg_hub_join", (7,))]
+    del calls[:]
+    with _lib.hub_forked("cuda:0") as hub:
+        hub.join()
+        assert len(calls) == 1
+    assert calls == [("cuda:0", "srg_hub_join", (7,))]
+    del calls[:]
+    with pytest.raises(KeyError):
+        with _lib.hub_forked("cuda:0") as hub:
+            hub.join()
+            raise KeyError("after the join")
+    assert len(calls) == 1
+    del calls[:]
+    with _lib.hub_forked("cuda:0", False) as hub:
+        hub.join()
+    assert calls == []

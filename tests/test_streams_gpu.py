@@ -62,6 +62,76 @@ def test_hub_nojoin_then_join_per_stream(oracle_mod):
         np.testing.assert_array_equal(y.cpu().numpy(), want)
 
 
+def _join(device):
+    from srgnn import _lib
+    _lib.call(device, "srg_hub_join", _lib.stream(device))
+
+
+def test_hub_join_with_nothing_forked(oracle_mod):
+    """srg_hub_join on a stream that never forked: SRG_OK, no side stream made for it, and the stream's
+    next hop is the oracle's."""
+    from srgnn import _lib
+    from srgnn.spmm import spmm
+    c = G.Case("rand_d128_r05")
+    A = _hub_csr(c)
+    x = c.x()
+    X = torch.from_numpy(x).cuda()
+    want = oracle_mod.spmm(*c.ahat(), x)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        before = _lib.query("srg_hub_side_streams")
+        assert _lib.lib().srg_hub_join(_lib.stream(X.device)) == _lib.SRG_OK
+        assert _lib.query("srg_hub_side_streams") == before
+        y = spmm(A, X)
+    s.synchronize()
+    np.testing.assert_array_equal(y.cpu().numpy(), want)
+
+
+def test_hub_pending_then_joined_launch_on_one_stream(oracle_mod):
+    """An unjoined fork, then a launch that joins its own fork, then srg_hub_join, all on one stream:
+    the side stream runs in order, so either join covers the first launch's hub rows too."""
+    from srgnn.spmm import spmm
+    c = G.Case("rand_d128_r05")
+    A = _hub_csr(c)
+    x = c.x()
+    X = torch.from_numpy(x).cuda()
+    want = oracle_mod.spmm(*c.ahat(), x)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        y0 = spmm(A, X, hub_nojoin=True)
+        y1 = spmm(A, X)
+        _join(X.device)
+        outs = [y0.clone(), y1.clone()]       # read after the join, on the same stream
+    s.synchronize()
+    for y in outs:
+        np.testing.assert_array_equal(y.cpu().numpy(), want)
+
+
+def test_hub_continue_without_and_with_a_pending_fork(oracle_mod):
+    """SRG_SPMM_HUB_CONTINUE with nothing pending is a real fork; a second such launch before the join
+    is the true continue (appended to the side stream, no new fork)."""
+    from srgnn.spmm import spmm
+    c = G.Case("rand_d128_r05")
+    A = _hub_csr(c)
+    x = c.x()
+    X = torch.from_numpy(x).cuda()
+    want = oracle_mod.spmm(*c.ahat(), x)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        # the outputs exist before the first fork: a continued launch's hub rows are ordered after that fork only
+        ys = [torch.empty((c.n, x.shape[1]), dtype=torch.float32, device="cuda") for _ in range(3)]
+        spmm(A, X, out=ys[0], hub_nojoin=True, hub_continue=True)
+        _join(X.device)
+        first = ys[0].clone()
+        spmm(A, X, out=ys[1], hub_nojoin=True, hub_continue=True)
+        spmm(A, X, out=ys[2], hub_nojoin=True, hub_continue=True)
+        _join(X.device)
+        outs = [first, ys[1].clone(), ys[2].clone()]
+    s.synchronize()
+    for y in outs:
+        np.testing.assert_array_equal(y.cpu().numpy(), want)
+
+
 def test_two_host_threads_two_streams(oracle_mod):
     """Two host threads issue hub-forking hops concurrently on their own streams."""
     from srgnn.spmm import propagate

@@ -120,8 +120,8 @@ def main():
                 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * a.reps)]
                 for r in range(a.reps):
                     ev[2 * r].record()
-                    op._hub_launch(src, dst[: op.rows])
-                    _lib.call(dev, "srg_hub_join", _lib.stream(dev))
+                    with _lib.hub_forked(dev):
+                        op._hub_launch(src, dst[: op.rows])
                     ev[2 * r + 1].record()
                 torch.cuda.synchronize()
                 ms = sorted(ev[2 * r].elapsed_time(ev[2 * r + 1]) for r in range(a.reps))
