@@ -381,12 +381,43 @@ int srg_spmm_cheby_f32(const int64_t* indptr, const int32_t* indices, const floa
  * order of element-wise steps (Python sum(): left to right from +0; torch's CPU dim-0 sum: 16-term
  * blocks folded in levels).  Per element, separate multiply / add / correctly rounded divide:
  *   SRG_ACC_INIT: agg = 0 + w*y     SRG_ACC_ADD: agg = agg + w*y     SRG_ACC_DIV: agg = agg / w
- * agg and y are device panels [n_rows, d] with leading dimensions lda / ldy (y unused for DIV). */
+ * agg and y are device panels [n_rows, d] with leading dimensions lda / ldy (y unused for DIV).
+ * The selecting modes ({min,max,concat}_message_op.py; w is ignored) move values as their 32 bits:
+ *   SRG_ACC_COPY: agg = y (not INIT with w = 1: 0 + (-0) is +0)
+ *   SRG_ACC_MIN:  if (!isnan(agg) && !(y >= agg)) agg = y
+ *   SRG_ACC_MAX:  if (!isnan(agg) && !(y <= agg)) agg = y
+ * -- torch's CPU min / max of the stacked hops applied hop by hop: the first NaN wins and sticks, a
+ * tie (-0 against +0 included) keeps the earlier hop.  Bit-identical to the reference. */
 #define SRG_ACC_INIT 0
 #define SRG_ACC_ADD 1
 #define SRG_ACC_DIV 2
+#define SRG_ACC_COPY 3
+#define SRG_ACC_MIN 4
+#define SRG_ACC_MAX 5
 int srg_hop_accumulate_f32(float* agg, int64_t lda, const float* y, int64_t ldy, int64_t n_rows,
                            int32_t d, float w, int mode, void* stream);
+
+/* One hop of the NAFS combination (SSRG/operators/message_operator/over_smooth_distance_op.py, the
+ * model of models/nafs.py) without the K+1 panels: per row r of the hop panel y, all in fp32,
+ *   s = ((x0[r].y[r]) / (sqrt(sum y[r]^2) + 1e-10f)) / n0[r]        e = expf(s)
+ *   acc[r,:] = (INIT ? 0 : acc[r,:]) + e * y[r,:]     z[r] = (INIT ? 0 : z[r]) + e     e_out[r*lde] = e
+ * with x0 hop 0 and n0[r] = sqrt(sum x0[r]^2) + 1e-10f.  SRG_SIM_HOP0 says y is hop 0 itself: x0 is
+ * not read (may be NULL) and n0 is written.  After the last hop srg_row_divide_f32 (acc[r,:] /= z[r])
+ * makes the weights e_k / sum_j e_j, the reference's softmax over the hops: s is a cosine, |s| <= 1, so
+ * no row maximum is subtracted and every hop is folded in as it appears.  e_out (NULL, or one float
+ * per row at stride lde) receives the hop's unnormalised weight.  Deterministic -- a row's bits
+ * depend on d and on the panels' alignment (16-, 8- or 4-byte accesses), not on n_rows or the
+ * launch -- and within (4d + 2T + 32) * 2^-24 * sum_k w_k |X_k[r,c]| of the exact value for T
+ * hops; not bit-identical to torch's CPU result, whose reduction order depends on the
+ * host's SIMD width.  x0, y, acc: device panels [n_rows, d] with leading dimensions ldx0 / ldy /
+ * lda; n0, z: [n_rows]; acc must not alias x0 or y. */
+#define SRG_SIM_INIT 0x1
+#define SRG_SIM_HOP0 0x2
+int srg_hop_simweight_f32(const float* x0, int64_t ldx0, const float* y, int64_t ldy, float* n0, float* acc,
+                          int64_t lda, float* z, float* e_out, int64_t lde, int64_t n_rows, int32_t d,
+                          uint32_t flags, void* stream);
+/* acc[r, :] = acc[r, :] / z[r] (correctly rounded), acc [n_rows, d] with leading dimension lda. */
+int srg_row_divide_f32(float* acc, int64_t lda, const float* z, int64_t n_rows, int32_t d, void* stream);
 
 /* srg_spmm_csr_f32 with the aggregation step fused into its epilogue: Y = A*X as above and, for
  * every element y stored, agg = (agg_init ? 0 : agg) + w*y (separate multiply / add) -- the same

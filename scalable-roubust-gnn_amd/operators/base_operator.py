@@ -11,7 +11,9 @@ reference's FloatCSRMulDenseOMP), and the K result panels come back in one batch
 `propagate_aggregate(adj, feature, msg_op)` is `msg_op.aggregate(self.propagate(adj, feature))` --
 the non-learnable branch of BaseSGModel.preprocess (SSRG/models/base_scalable/base_model.py:34-44)
 -- without the hop list: srgnn.aggregate folds each hop into the result as it is produced, in the
-reference's own summation order (bit-identical), so only 4-5 panels are ever resident.
+reference's own summation order (bit-identical), so only 4-5 panels are ever resident.  min, max and
+concat are bit-identical too; NAFS's OverSmoothDistanceWeightedOp is deterministic and within a derived
+rounding bound of the exact formula (srgnn/aggregate.py).
 """
 from __future__ import annotations
 
@@ -149,8 +151,10 @@ class GraphOp:
 
     def propagate_aggregate(self, adj, feature, msg_op, device=None, to_host=True):
         """msg_op.aggregate(self.propagate(adj, feature)) for msg_op in last / sum / mean /
-        simple_weighted, computed on the GPU without materialising the K+1 hops.  Same checks
-        and errors as propagate(); learnable message ops raise ValueError (they need the list)."""
+        simple_weighted / min / max / concat (bit-identical) and over_smooth_dis_weighted (NAFS:
+        deterministic, within the rounding bound of srgnn.aggregate), computed on the GPU without
+        materialising the K+1 hops.  Same checks and errors as propagate(); learnable message ops
+        raise ValueError (they need the list and autograd)."""
         from srgnn.aggregate import fused_combine
         if isinstance(feature, Tensor) and feature.is_cuda:
             A = self._build_operator(adj, feature.device)

@@ -39,6 +39,11 @@ SRG_CHEBY_HUB_NOJOIN = 0x20
 SRG_ACC_INIT = 0
 SRG_ACC_ADD = 1
 SRG_ACC_DIV = 2
+SRG_ACC_COPY = 3
+SRG_ACC_MIN = 4
+SRG_ACC_MAX = 5
+SRG_SIM_INIT = 0x1
+SRG_SIM_HOP0 = 0x2
 SRG_TAIL_MAX = 32
 
 SRG_SPGEMM_SERIAL_B = 0x1
@@ -90,6 +95,8 @@ EXPORTED_SYMBOLS = (
     "srg_cheby_step_f32",
     "srg_cheby_epilogue_f32",
     "srg_hop_accumulate_f32",
+    "srg_hop_simweight_f32",
+    "srg_row_divide_f32",
     "srg_spmm_agg_f32",
     "srg_spmm_span_f32",
     "srg_spmm_cheby_f32",
@@ -195,6 +202,10 @@ def _declare(lib):
     lib.srg_spmm_cheby_f32.restype = ctypes.c_int
     lib.srg_hop_accumulate_f32.argtypes = [_p, _i64, _p, _i64, _i64, _i32, _f32, ctypes.c_int, _p]
     lib.srg_hop_accumulate_f32.restype = ctypes.c_int
+    lib.srg_hop_simweight_f32.argtypes = [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _i64, _i64, _i32, _u32, _p]
+    lib.srg_hop_simweight_f32.restype = ctypes.c_int
+    lib.srg_row_divide_f32.argtypes = [_p, _i64, _p, _i64, _i32, _p]
+    lib.srg_row_divide_f32.restype = ctypes.c_int
     lib.srg_tail_record_f32.argtypes = [_p, _p, _i64, _i32, _i64, _i32, _f32, _p]
     lib.srg_tail_record_f32.restype = ctypes.c_int
     lib.srg_tail_rowsum_f32.argtypes = [_p, _i64, _i32, _i64, _i32, _p, _i32, _p]

@@ -9,9 +9,14 @@ base_scalable/base_model.py:34-44, via the MessageOp of the model):
     mean            sum(feat_list[start:end]) / (end - start)       (mean_message_op.py:9-10)
     simple_weighted one_dim_weighted_add(feat_list[start:end], w)   (simple_weighted_message_op.py:36-53,
                     w = [alpha, alpha(1-alpha), ...][start:end] or a hand-crafted list;  utils.py:426-437)
+    min / max       stack(feat_list[start:end]).min / max(dim=0)[0] (min_message_op.py, max_message_op.py)
+    concat          hstack(feat_list[start:end])                    (concat_message_op.py)
+    over_smooth     NAFS: per node, hop k weighted by the softmax over the hops of its cosine similarity
+                    to hop 0                                        (over_smooth_distance_op.py:11-33)
 
 Here the hops run on the GPU with two ping-pong panels and one or two accumulators: memory is
 4-5 panels instead of K+1 (papers100M-sized features fit one MI355X), nothing goes to the host.
+concat writes every hop of its slice straight into its column slice of the [n, T*d] result.
 
 Exactness.  Python's sum() is ((0 + f0) + f1) + ...; one_dim_weighted_add is torch's CPU dim-0
 sum of the rounded products f_k * w_k over the flattened [T, n*d] stack, whose order is ATen's
@@ -20,6 +25,12 @@ last (n*d mod 32) flat elements the scalar row_sum order (4 interleaved partials
 plans exactly that order as element-wise steps (INIT / ADD / DIV / fold / tail), which the HIP
 kernels execute with separate multiply / add / divide -- bit-identical to the reference on the
 same hops.  (For n*d == 1 torch uses its whole-tensor reduction: exact only below 8 terms.)
+min, max and concat select values, hop by hop in torch's order (the first NaN sticks, a tie keeps
+the earlier hop): bit-identical too, signs of zero and NaNs included.  The NAFS weights are
+e_k / sum_j e_j with e_k = expf(cosine_k), folded in one pass (srg_hop_simweight_f32): deterministic,
+the same bits under every column blocking, and within (4d + 2(K+1) + 32) * 2^-24 * sum_k w_k |X_k|
+of the exact value per element -- torch's own CPU result depends on the host's SIMD width, so there
+are no reference bits to match.
 """
 from __future__ import annotations
 
@@ -36,7 +47,8 @@ def _slice_indices(n: int, start, end):
 
 def combine_plan(msg_op, n_hops: int):
     """(mode, [(hop, fp32 weight)], divisor) reproducing `msg_op.combine(feat_list)` for a list of
-    n_hops = K + 1 panels.  Raises ValueError for learnable / non-linear message operators."""
+    n_hops = K + 1 panels.  Modes "min" / "max" / "concat" carry the hops of feat_list[start:end]
+    and "over_smooth" all hops (weight 1.0: unused).  Raises ValueError for learnable operators."""
     aggr = getattr(msg_op, "aggr_type", None)
     start, end = getattr(msg_op, "start", None), getattr(msg_op, "end", None)
     if aggr == "last":
@@ -63,7 +75,17 @@ def combine_plan(msg_op, n_hops: int):
         if len(w32) != len(hops):
             raise ValueError("The feature list and the weight list have different lengths!")
         return "weighted", list(zip(hops, w32)), None
-    raise ValueError(f"message operator {aggr!r} has no fused form (learnable or non-linear)")
+    if aggr in ("min", "max", "concat"):
+        hops = _slice_indices(n_hops, start, end)
+        if not hops:
+            raise ValueError(f"empty hop slice: the reference's {'hstack' if aggr == 'concat' else 'stack'} "
+                             "of it raises too")
+        return aggr, [(k, 1.0) for k in hops], None
+    if aggr == "over_smooth_dis_weighted":
+        if n_hops < 1:
+            raise ValueError("the NAFS combination needs hop 0")
+        return "over_smooth", [(k, 1.0) for k in range(n_hops)], None
+    raise ValueError(f"message operator {aggr!r} has no fused form (learnable)")
 
 
 def tail_range(n: int, d: int):
@@ -118,6 +140,68 @@ def combine_steps(mode: str, terms, divisor=None):
     return out
 
 
+SELECT_MODES = ("min", "max", "concat", "over_smooth")
+
+
+def _accumulate(agg, y, w, mode):
+    """One srg_hop_accumulate_f32 step on agg's device and torch's current stream."""
+    n, d = agg.shape
+    _lib.call(agg.device, "srg_hop_accumulate_f32", agg.data_ptr(), agg.stride(0),
+              y.data_ptr() if y is not None else None, y.stride(0) if y is not None else agg.stride(0),
+              n, d, float(w), mode, _lib.stream(agg.device))
+
+
+class _DeviceSelect:
+    """min / max / concat / over_smooth, hop by hop through the C-ABI (torch's current stream).
+    target(k): the panel hop k's SpMM should write (concat: its column slice), or None for a scratch
+    panel; consume(k, panel) folds hop k in; hops must come in increasing order."""
+
+    def __init__(self, mode, hops, n, d, device):
+        self.mode, self.hops, self.n, self.d, self.device = mode, list(hops), n, d, device
+        f32 = dict(dtype=torch.float32, device=device)
+        if mode == "concat":
+            self.out = torch.empty((n, len(self.hops) * d), **f32)
+            self.slices = {k: self.out[:, j * d:(j + 1) * d] for j, k in enumerate(self.hops)}
+        else:
+            self.out = torch.empty((n, d), **f32)
+            self.slices = {}
+        if mode == "over_smooth":
+            self.n0, self.z = torch.empty(n, **f32), torch.empty(n, **f32)
+            self.x0 = None
+        self.first = True
+
+    @property
+    def last(self):
+        return self.hops[-1]
+
+    def target(self, k):
+        return self.slices.get(k)
+
+    def consume(self, k, panel):
+        if k not in self.hops:
+            return
+        if self.mode == "concat":
+            if panel is not self.slices[k]:
+                _accumulate(self.slices[k], panel, 1.0, _lib.SRG_ACC_COPY)
+        elif self.mode in ("min", "max"):
+            mode = _lib.SRG_ACC_COPY if self.first else _lib.SRG_ACC_MIN if self.mode == "min" else _lib.SRG_ACC_MAX
+            _accumulate(self.out, panel, 1.0, mode)
+        else:
+            if self.first:
+                self.x0 = panel
+            flags = (_lib.SRG_SIM_INIT | _lib.SRG_SIM_HOP0) if self.first else 0
+            _lib.call(self.device, "srg_hop_simweight_f32", self.x0.data_ptr(), self.x0.stride(0), panel.data_ptr(),
+                      panel.stride(0), self.n0.data_ptr(), self.out.data_ptr(), self.out.stride(0),
+                      self.z.data_ptr(), None, 0, self.n, self.d, flags, _lib.stream(self.device))
+        self.first = False
+
+    def result(self):
+        if self.mode == "over_smooth":
+            _lib.call(self.device, "srg_row_divide_f32", self.out.data_ptr(), self.out.stride(0),
+                      self.z.data_ptr(), self.n, self.d, _lib.stream(self.device))
+        return self.out
+
+
 class _DeviceSteps:
     """Executes combine_steps on the device through the C-ABI (one stream, torch's current)."""
 
@@ -134,9 +218,7 @@ class _DeviceSteps:
                                                              device=self.device)
 
     def _acc(self, agg, y, w, mode):
-        _lib.call(self.device, "srg_hop_accumulate_f32", agg.data_ptr(), agg.stride(0),
-                  y.data_ptr() if y is not None else None, y.stride(0) if y is not None else agg.stride(0),
-                  self.n, self.d, float(w), mode, self.stream)
+        _accumulate(agg, y, w, mode)
 
     def run(self, s, hop_panel=None):
         kind = s[0]
@@ -276,9 +358,74 @@ def propagate_aggregate(A: DeviceCSR, X: torch.Tensor, K: int, steps=None, last_
     return ex.result()
 
 
-def fused_combine(A: DeviceCSR, X: torch.Tensor, K: int, msg_op) -> torch.Tensor:
-    """msg_op.combine([X, ÂX, …, Â^K X]) computed on the device without the hop list."""
+def propagate_select(A: DeviceCSR, X: torch.Tensor, K: int, mode: str, hops, col_blocks=None):
+    """The min / max / concat / over_smooth combination of `hops` (increasing hop indices <= K) of
+    [X, ÂX, …, Â^K X]: the same hop loop as propagate_aggregate -- two ping-pong panels, hops beyond
+    the last one needed not computed -- with each hop folded in as it appears.  concat's hops are
+    written by their SpMM straight into their column slice of the [n, T*d] result, and the next hop
+    gathers from that slice."""
+    n, d = X.shape
+    if A.n_rows != n or A.n_cols != n:
+        raise ValueError("propagate_select needs a square operator matching X")
+    if X.dim() != 2 or X.dtype != torch.float32 or X.stride(1) != 1 or X.stride(0) < d:
+        raise ValueError("X must be a row-major float32 [n, d] device panel")
+    hops = list(hops)
+    if mode not in SELECT_MODES or not hops or hops != sorted(set(hops)) or hops[0] < 0 or hops[-1] > K:
+        raise ValueError(f"mode {mode!r} over hops {hops} of a {K}-hop run")
+    from .spmm import prepare
+    ex = _DeviceSelect(mode, hops, n, d, X.device)
+    last = ex.last
+    col_blocks = prepare(A, d, last, col_blocks) if last > 0 else 1
+    ex.consume(0, X)
+    cur = X
+    scratch = []
+    for k in range(1, last + 1):
+        nxt = ex.target(k)
+        if nxt is None:
+            free = [p for p in scratch if p is not cur]
+            if not free:
+                free = [torch.empty((n, d), dtype=torch.float32, device=X.device)]
+                scratch.append(free[0])
+            nxt = free[0]
+        hop(A, cur, nxt, col_blocks=col_blocks)
+        cur = nxt
+        ex.consume(k, cur)
+    return ex.result()
+
+
+def fused_combine(A: DeviceCSR, X: torch.Tensor, K: int, msg_op, col_blocks=None) -> torch.Tensor:
+    """msg_op.combine([X, ÂX, …, Â^K X]) computed on the device without the hop list.
+    col_blocks: column blocks per hop (spmm.hop; None = auto_col_blocks); the same bits either way."""
     mode, terms, div = combine_plan(msg_op, K + 1)
     if mode == "last":
-        return propagate_aggregate(A, X, K, last_only=True)
-    return propagate_aggregate(A, X, K, combine_steps(mode, terms, div))
+        return propagate_aggregate(A, X, K, last_only=True, col_blocks=col_blocks)
+    if mode in SELECT_MODES:
+        return propagate_select(A, X, K, mode, [k for k, _ in terms], col_blocks=col_blocks)
+    return propagate_aggregate(A, X, K, combine_steps(mode, terms, div), col_blocks=col_blocks)
+
+
+def combine_device(msg_op, feat_list) -> torch.Tensor:
+    """msg_op.combine(feat_list) on a list of device panels the caller already holds (for example
+    GraphOp.propagate_device's): the steps fused_combine runs, without the hops.  last returns
+    feat_list[-1] itself, as the reference does; every other result is a new panel."""
+    if not isinstance(feat_list, (list, tuple)) or not feat_list:
+        raise TypeError("feat_list must be a non-empty list of device panels")
+    n, d = feat_list[0].shape
+    for k, p in enumerate(feat_list):
+        if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.float32 or p.dim() != 2 \
+                or tuple(p.shape) != (n, d) or p.stride(1) != 1 or (n > 1 and p.stride(0) < d) \
+                or p.device != feat_list[0].device:
+            raise ValueError(f"feat_list[{k}] must be a row-major float32 [{n}, {d}] panel on one HIP device")
+    mode, terms, div = combine_plan(msg_op, len(feat_list))
+    if mode == "last":
+        return feat_list[-1]
+    if mode in SELECT_MODES:
+        ex = _DeviceSelect(mode, [k for k, _ in terms], n, d, feat_list[0].device)
+        for k in ex.hops:
+            ex.consume(k, feat_list[k])
+        return ex.result()
+    ex = _DeviceSteps(n, d, feat_list[0].device)
+    for s in combine_steps(mode, terms, div):
+        k = step_hop(s)
+        ex.run(s, feat_list[k] if k is not None else None)
+    return ex.result()
