@@ -455,12 +455,20 @@ int srg_tail_rowsum_f32(float* agg, int64_t lda, int32_t d, int64_t flat_start, 
 
 /* construct_adj on the device (SSRG/operators/utils.py:81-93, adj_to_symmetric_norm): out[s] =
  * ((0 + v[p[s]]) + v[p[s]+1]) + ... over vals[seg_ptr[s] .. seg_ptr[s+1]) in fp64, left to right
- * -- the order in which scipy merges duplicate entries of adj + I and sums the rows for the
- * degrees.  seg_ptr has n_seg + 1 entries; all pointers are device pointers. */
+ * -- the order in which scipy merges duplicate entries of adj + I (the row sums of the degrees
+ * are srg_segment_sum_numpy_f64).  seg_ptr has n_seg + 1 entries; all pointers are device pointers. */
 int srg_segment_sum_f64(const int64_t* seg_ptr, const double* vals, int64_t n_seg, double* out, void* stream);
 /* The same in fp32: the directed families' fp32 normalisations (SSRG/operators/utils.py:195-424:
  * torch_scatter.scatter_add over fp32 edge weights, a sequential sum in element order). */
 int srg_segment_sum_f32(const int64_t* seg_ptr, const float* vals, int64_t n_seg, float* out, void* stream);
+
+/* The row degrees of adj_to_symmetric_norm in the order of scipy's csr.sum(1), which is
+ * np.add.reduceat: out[s] = a[0] + pairwise(a[1:]) over a = vals[seg_ptr[s] .. seg_ptr[s+1]), with
+ * numpy's pairwise sum (fewer than 8 elements left to right; up to 128 in eight strided accumulators
+ * folded as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus the remainder left to right; longer runs split
+ * at n/2 rounded down to a multiple of 8).  An empty segment gives +0.  fp64 only. */
+int srg_segment_sum_numpy_f64(const int64_t* seg_ptr, const double* vals, int64_t n_seg, double* out,
+                              void* stream);
 
 /* fp64 Y = A * X (X [rows of A's columns, d], ldx; Y [n_rows, d], ldy) in scipy's csr_matvec(s)
  * order (each element from 0, adding the separately rounded product of every stored entry in

@@ -5,10 +5,12 @@ bench.py's cpu_baseline leg may import this module; the product (scalable-roubus
 does, and it must not be used as a fallback.
 
   sym_norm        restates adj_to_symmetric_norm      SSRG/operators/utils.py:81-93
+  row_sum_numpy   restates scipy's csr.sum(1), i.e. np.add.reduceat: a[0] + pairwise(a[1:]) per row
   spmm / propagate restate FloatCSRMulDenseOMP + the   SSRG/operators/csrc/matmul.c:23-40,
                   GraphOp hop loop                     SSRG/operators/base_operator.py:19-36
   spmm64          fp64 product in scipy's csr_matvecs order (the directed families' power iterations)
-  segment_sum     sequential per-segment sums (scatter_add / duplicate merges), any float dtype
+  segment_sum     sequential per-segment sums (scatter_add / duplicate merges), any float dtype;
+                  not the order of a row sum (row_sum_numpy)
   ref_spmm        the reference's own matmul.c, compiled from its source by oracle/Makefile into
                   oracle/_ref/libmatmul_ref.so (the shipped prebuilt libmatmul.so is never loaded)
   combine         restates MessageOp.combine for last / sum / mean / simple_weighted with the same
@@ -22,7 +24,9 @@ does, and it must not be used as a fallback.
                   against a dense eigendecomposition.
 
 Pinning: sym_norm/spmm/propagate are checked against tests/golden/*.npz, produced by running the
-reference's own Python operators (tests/golden/make_golden.py), and spmm against ref_spmm.
+reference's own Python operators (tests/golden/make_golden.py; the weighted cw_* cases with
+non-dyadic weights, zero and negative degrees by make_golden_construct.py), row_sum_numpy against
+the installed scipy (tests/test_construct_scipy_cpu.py), and spmm against ref_spmm.
 """
 from __future__ import annotations
 
@@ -113,32 +117,81 @@ def _sum_duplicates_sorted(rows, cols, vals, n):
     return key // n, key % n, vals
 
 
+PW_BLOCK = 128      # numpy's PW_BLOCKSIZE
+
+
+def _pairwise_sum(a, block=PW_BLOCK, align=8, unroll=True):
+    """numpy's pairwise sum of a 1-D fp64 array (numpy/_core/src/umath/loops_utils.h.src,
+    @TYPE@_pairwise_sum).  The keywords exist for the tests' mutants only."""
+    n = a.size
+    if n < 8 or (n <= block and not unroll):
+        res = np.float64(-0.0)
+        for x in a:
+            res = res + x
+        return res
+    if n <= block:
+        r = a[:8].copy()                       # eight accumulators, stride 8
+        i = 8
+        while i < n - n % 8:
+            r += a[i:i + 8]
+            i += 8
+        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+        for x in a[i:]:
+            res = res + x
+        return res
+    n2 = n // 2
+    n2 -= n2 % align
+    return _pairwise_sum(a[:n2], block, align, unroll) + _pairwise_sum(a[n2:], block, align, unroll)
+
+
+def row_sum_numpy(ptr, vals, head_outside=True, **kw):
+    """The fp64 row sums of scipy's csr.sum(1): _cs_matrix._minor_reduce is np.add.reduceat over
+    the non-empty rows, and per row the add loop computes a[0] + pairwise(a[1:]); an empty row
+    keeps +0.  Restated without reduceat; tests pin it to the installed scipy / numpy bit for bit."""
+    ptr = np.asarray(ptr, dtype=np.int64)
+    vals = np.asarray(vals, dtype=np.float64)
+    out = np.zeros(ptr.size - 1, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for s in range(ptr.size - 1):
+            a = vals[ptr[s]:ptr[s + 1]]
+            if a.size == 1:
+                out[s] = a[0]
+            elif a.size and head_outside:
+                out[s] = a[0] + _pairwise_sum(a[1:], **kw)
+            elif a.size:
+                out[s] = _pairwise_sum(a, **kw)
+    return out
+
+
 def sym_norm(indptr, indices, data, n, r):
     """Â = D^(r-1) (A+I)^T D^(-r), D = rowsum(A+I) (fp64), as CSR arrays.
 
     Returns (indptr int64, indices int32, values fp64).  Element (i, j) is
-    ((A+I)[j, i] * deg_i^(r-1)) * deg_j^(-r), products evaluated in that order (fp64), with
-    np.power for the degree powers and inf -> 0, zero products dropped (scipy's sparse products
-    keep only nonzero results)."""
+    ((A+I)[j, i] * deg_i^(r-1)) * deg_j^(-r), products evaluated in that order (fp64), with the
+    degrees summed in scipy's order (row_sum_numpy), np.power for the degree powers and inf -> 0.
+    The reference scales by sp.diags(left) / sp.diags(right): a zero on either diagonal is not
+    stored, so its entries are absent whatever the other factor is (NaN included), and scipy's
+    sparse products keep only nonzero results, so zero products are dropped too."""
     rows, cols, vals = _coo(indptr, indices, data, n)
     diag = np.arange(n, dtype=np.int64)
     rows, cols, vals = _sum_duplicates_sorted(np.r_[rows, diag], np.r_[cols, diag],
                                               np.r_[vals, np.ones(n)], n)
-    deg = np.zeros(n, dtype=np.float64)
-    for i, v in zip(rows.tolist(), vals.tolist()):   # sequential fp64 row sums, column order
-        deg[i] += v
-    with np.errstate(divide="ignore"):
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(ptr, rows + 1, 1)
+    deg = row_sum_numpy(np.cumsum(ptr), vals)
+    with np.errstate(divide="ignore", invalid="ignore"):
         left = np.power(deg, r - 1)
         right = np.power(deg, -r)
     left[np.isinf(left)] = 0.0
     right[np.isinf(right)] = 0.0
     # (A+I)[j, i] lands at (i, j)
     t_rows, t_cols = cols, rows
-    step1 = vals * left[t_rows]          # (A+I)[j,i] * left[i]
-    step2 = step1 * right[t_cols]        # ... * right[j]
-    keep1 = step1 != 0
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        step1 = vals * left[t_rows]          # (A+I)[j,i] * left[i]
+        step2 = step1 * right[t_cols]        # ... * right[j]
+    keep1 = (left[t_rows] != 0) & (step1 != 0)
     t_rows, t_cols, step2 = t_rows[keep1], t_cols[keep1], step2[keep1]
-    keep2 = step2 != 0
+    keep2 = (right[t_cols] != 0) & (step2 != 0)
     t_rows, t_cols, step2 = t_rows[keep2], t_cols[keep2], step2[keep2]
     order = np.lexsort((t_cols, t_rows))
     t_rows, t_cols, step2 = t_rows[order], t_cols[order], step2[order]

@@ -1751,12 +1751,13 @@ __global__ void k_tail_rowsum(float* __restrict__ agg, int64_t lda, int d, int64
 }
 
 // ------------------------------------------------------------------------------------------------
-// construct_adj on the device: sequential fp64 segment sums (duplicate merging and row degrees in
-// storage order, starting from +0 -- scipy's csr_binop / csr_matvec accumulation order)
+// construct_adj on the device: sequential fp64 segment sums (duplicate merging in storage order,
+// starting from +0 -- scipy's csr_binop / sum_duplicates accumulation order; the directed families'
+// scatter sums and the wavelet row normalisation).  The row degrees are k_segment_sum_numpy's.
 // ------------------------------------------------------------------------------------------------
 // One wave per 64 consecutive segments.  A segment of at most kSegShort entries is summed by its
-// own lane; a longer one (the degree of a hub row: 155,868 entries on the products-shaped graph,
-// 30 ms as a one-lane loop of dependent loads) by the whole wave: the values are read 64 at a time
+// own lane; a longer one (a hub row: 155,868 entries on the products-shaped graph, 30 ms as a
+// one-lane loop of dependent loads) by the whole wave: the values are read 64 at a time
 // with one coalesced load, the next block prefetched, and the sequential sum runs over them
 // through v_readlane -- the same adds in the same order.
 constexpr int64_t kSegShort = 64;
@@ -1809,6 +1810,119 @@ k_segment_sum(const int64_t* __restrict__ seg_ptr, const T* __restrict__ vals, i
                 for (int q = 0; q < nb; ++q) acc = e_add(acc, bcast_lane(v, q));
             }
             if (lane == 0) out[w * 64 + l] = acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// construct_adj on the device: row degrees in numpy's order.  scipy's csr.sum(1) is
+// np.add.reduceat over the non-empty rows, and per row that is a[0] + pairwise(a[1:]) with numpy's
+// pairwise sum: fewer than 8 elements sequentially; up to kNpLeaf in eight strided accumulators
+// folded as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus a sequential remainder; anything longer
+// split at n/2 rounded down to a multiple of 8, left half first.
+// ------------------------------------------------------------------------------------------------
+constexpr int64_t kNpLeaf = 128;
+
+__device__ __forceinline__ int64_t np_split(int64_t n) { return (n >> 1) & ~(int64_t)7; }
+
+// 1 <= n <= kNpLeaf (numpy starts from -0.0, and -0.0 + a[0] is a[0])
+__device__ __forceinline__ double np_leaf_sum(const double* __restrict__ a, int n)
+{
+    if (n < 8) {
+        double res = a[0];
+        for (int i = 1; i < n; ++i) res = e_add(res, a[i]);
+        return res;
+    }
+    double r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = a[k];
+    int i = 8;
+    for (; i < n - (n & 7); i += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = e_add(r[k], a[i + k]);
+    }
+    double res = e_add(e_add(e_add(r[0], r[1]), e_add(r[2], r[3])), e_add(e_add(r[4], r[5]), e_add(r[6], r[7])));
+    for (; i < n; ++i) res = e_add(res, a[i]);
+    return res;
+}
+
+// One wave per 64 consecutive segments, as k_segment_sum.  A segment whose pairwise part fits one
+// leaf is summed by its own lane.  A longer one is taken by the whole wave: every leaf of the
+// recursion holds 64..128 elements, so it contains a multiple of 64 and lane l looks up the leaf
+// around element 64 * (t0 + l) and, if that is the leaf's first multiple, sums it -- up to 64
+// independent leaves at a time.  The wave then walks the leaves left to right (uniform control
+// flow) and folds the tree in the recursion's order: a finished left child waits in lane `depth`
+// of `pend` until its right sibling is complete.
+__global__ void __launch_bounds__(256)
+k_segment_sum_numpy(const int64_t* __restrict__ seg_ptr, const double* __restrict__ vals, int64_t n_seg,
+                    double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_stride = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w * 64 < n_seg;
+         w += wave_stride) {
+        const int64_t s = w * 64 + lane;
+        const bool valid = s < n_seg;
+        const int64_t beg = valid ? seg_ptr[s] : 0;
+        const int64_t end = valid ? seg_ptr[s + 1] : 0;
+        const int64_t len = end - beg;
+        const bool wide = len - 1 > kNpLeaf;
+        const double head = len > 0 ? vals[beg] : 0.0;
+        if (valid && !wide)
+            out[s] = len > 1 ? e_add(head, np_leaf_sum(vals + beg + 1, (int)(len - 1))) : head;
+        unsigned long long todo = __ballot(wide);   // wave-uniform
+        while (todo) {
+            const int l = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int64_t b = bcast_lane(beg, l) + 1;
+            const int64_t m = bcast_lane(end, l) - b;        // the pairwise part a[1:], m > kNpLeaf
+            const double* __restrict__ a = vals + b;
+            double pend = 0.0, leaf = 0.0, v = 0.0;
+            int64_t t0 = -64;                                // first multiple of 64 the lanes hold
+            for (int64_t pos = 0; pos < m;) {
+                int64_t o = 0, k = m;
+                unsigned long long path = 0;                 // bit d: went right at depth d
+                int depth = 0;
+                while (k > kNpLeaf) {
+                    const int64_t n2 = np_split(k);
+                    if (pos < o + n2) {
+                        k = n2;
+                    } else {
+                        o += n2;
+                        k -= n2;
+                        path |= 1ull << depth;
+                    }
+                    ++depth;
+                }
+                const int64_t t = (o + 63) >> 6;             // o == pos
+                if (t - t0 >= 64) {
+                    t0 = t;
+                    const int64_t p = (t0 + lane) << 6;
+                    leaf = 0.0;
+                    if (p < m) {
+                        int64_t lo = 0, lk = m;
+                        while (lk > kNpLeaf) {
+                            const int64_t n2 = np_split(lk);
+                            if (p < lo + n2) {
+                                lk = n2;
+                            } else {
+                                lo += n2;
+                                lk -= n2;
+                            }
+                        }
+                        if (p - lo < 64) leaf = np_leaf_sum(a + lo, (int)lk);
+                    }
+                }
+                v = bcast_lane(leaf, (int)(t - t0));
+                while (depth > 0 && ((path >> (depth - 1)) & 1)) {
+                    --depth;
+                    v = e_add(bcast_lane(pend, depth), v);
+                }
+                if (depth > 0 && lane == depth - 1) pend = v;
+                pos = o + k;
+            }
+            const double h = bcast_lane(head, l);
+            if (lane == 0) out[w * 64 + l] = e_add(h, v);
         }
     }
 }
@@ -3145,6 +3259,19 @@ int srg_segment_sum_f64(const int64_t* seg_ptr, const double* vals, int64_t n_se
 int srg_segment_sum_f32(const int64_t* seg_ptr, const float* vals, int64_t n_seg, float* out, void* stream)
 {
     return launch_segment_sum<float>(seg_ptr, vals, n_seg, out, stream);
+}
+
+int srg_segment_sum_numpy_f64(const int64_t* seg_ptr, const double* vals, int64_t n_seg, double* out, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    if (n_seg < 0) return srg_fail(SRG_ERR_INVALID, "n_seg=%lld < 0", (long long)n_seg);
+    if (n_seg == 0) return srg_ok();
+    if (!seg_ptr || !out) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_seg + 255) / 256, 1 << 16);   // 64 segments per wave
+    hipLaunchKernelGGL(k_segment_sum_numpy, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       seg_ptr, vals, n_seg, out);
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
 }
 
 int srg_spmm_csr_f64(const int64_t* indptr, const int32_t* indices, const double* values, int64_t n_rows,

@@ -86,7 +86,8 @@ class GraphOp:
         raise NotImplementedError
 
     def construct_adj_device(self, adj, device):
-        """(indptr, indices, values fp64) device tensors of construct_adj(adj), bit-identical, or
+        """(indptr, indices, values fp64) device tensors of construct_adj(adj), bit-identical (see
+        srgnn/construct.py for the one caveat, non-canonical weighted input), or
         None when the operator has no device form (the host construct_adj is used then)."""
         return None
 

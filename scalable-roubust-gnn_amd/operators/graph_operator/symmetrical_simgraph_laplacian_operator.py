@@ -15,6 +15,9 @@ class SymLaplacianGraphOp(GraphOp):
         return adj_to_symmetric_norm(adj.tocoo(), self.r).tocsr()
 
     def construct_adj_device(self, adj, device):
-        """construct_adj on the GPU (srgnn.construct.sym_norm), bit-identical to the host scipy."""
+        """construct_adj on the GPU (srgnn.construct.sym_norm): the host construct_adj's fp64 values bit
+        for bit for a canonical adj (sorted rows, no duplicates), weighted or not, zero and negative
+        degrees included (NaN payloads apart); for a non-canonical weighted adj scipy adds a row of
+        adj + I in its own merge order, so a degree may differ in the last bit."""
         from srgnn.construct import sym_norm
         return sym_norm(adj.indptr, adj.indices, adj.data, adj.shape[0], self.r, device=device)

@@ -21,6 +21,9 @@ class PprGraphOp(GraphOp):
         return ((1 - self.alpha) * norm + self.alpha * sp.eye(adj.shape[0])).tocsr()
 
     def construct_adj_device(self, adj, device):
-        """construct_adj on the GPU (srgnn.construct.ppr_norm), bit-identical to the host scipy."""
+        """construct_adj on the GPU (srgnn.construct.ppr_norm): the host construct_adj's fp64 values bit
+        for bit for a canonical adj (sorted rows, no duplicates), weighted or not, zero and negative
+        degrees included (NaN payloads apart); for a non-canonical weighted adj scipy adds a row of
+        adj + I in its own merge order, so a degree may differ in the last bit."""
         from srgnn.construct import ppr_norm
         return ppr_norm(adj.indptr, adj.indices, adj.data, adj.shape[0], self.r, self.alpha, device=device)

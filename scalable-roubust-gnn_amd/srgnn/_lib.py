@@ -104,6 +104,7 @@ EXPORTED_SYMBOLS = (
     "srg_tail_rowsum_f32",
     "srg_segment_sum_f64",
     "srg_segment_sum_f32",
+    "srg_segment_sum_numpy_f64",
     "srg_spmm_csr_f64",
     "srg_gather_rows_f32",
     "srg_spgemm_scratch_bytes",
@@ -214,6 +215,8 @@ def _declare(lib):
     lib.srg_segment_sum_f64.restype = ctypes.c_int
     lib.srg_segment_sum_f32.argtypes = [_p, _p, _i64, _p, _p]
     lib.srg_segment_sum_f32.restype = ctypes.c_int
+    lib.srg_segment_sum_numpy_f64.argtypes = [_p, _p, _i64, _p, _p]
+    lib.srg_segment_sum_numpy_f64.restype = ctypes.c_int
     lib.srg_spmm_csr_f64.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p]
     lib.srg_spmm_csr_f64.restype = ctypes.c_int
     lib.srg_gather_rows_f32.argtypes = [_p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p]

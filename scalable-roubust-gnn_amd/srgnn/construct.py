@@ -3,15 +3,24 @@ from any scipy-style adjacency, bit-identical to the reference's scipy arithmeti
 
 Reference (SSRG/operators/utils.py:81-93, symmetrical_simgraph_ppr_operator.py:13-21):
     adj = adj + I                                   duplicates merged left to right, zeros dropped
-    deg = adj.sum(1)                                fp64 row sums in column order
+    deg = adj.sum(1)                                fp64 row sums: np.add.reduceat, per row
+                                                    a[0] + pairwise(a[1:]) in column order
     left = deg^(r-1), right = deg^(-r)              np.power, inf -> 0
-    Â = (adj . diag(left))^T . diag(right)          Â[i, j] = ((A+I)[j, i] * left[i]) * right[j]
+    Â = (adj . diag(left))^T . diag(right)          Â[i, j] = ((A+I)[j, i] * left[i]) * right[j];
+                                                    a zero left[i] or right[j] is not stored in
+                                                    sp.diags, so its entries are absent (even
+                                                    where the other factor is NaN), and so are
+                                                    zero products
     PPR: (1 - alpha) * Â + alpha * I
-Every step is an elementwise fp64 product, a sort, or a sequential segment sum
-(srg_segment_sum_f64), so the device result equals scipy's bit for bit; np.power stays on the
-host (N values through the same libm call as the reference).  Canonical inputs are pinned by the
-golden fixtures; for non-canonical weighted inputs scipy sums a row in its own merge order, so
-the last fp64 bit may differ there (integer weights are exact in any order).
+Every step is an elementwise fp64 product, a sort, a sequential segment sum for the duplicates
+(srg_segment_sum_f64) or a row sum in numpy's pairwise order (srg_segment_sum_numpy_f64), so the
+device result equals scipy's bit for bit; np.power stays on the host (N values through the same
+libm call as the reference).  Canonical inputs -- binary, dyadic and arbitrary fp64 weights,
+zero and negative degrees -- are pinned by the golden fixtures (the reference's own output).  For
+a non-canonical input (unsorted rows, duplicates) scipy's general csr_plus_csr emits each row of
+adj + I in its own linked-list order, not in column order, so the row sum adds the same values in
+another order and the last fp64 bit of a degree may differ there (integer weights are exact in
+any order).
 """
 from __future__ import annotations
 
@@ -29,6 +38,25 @@ def segment_sum_device(seg_ptr: torch.Tensor, vals: torch.Tensor) -> torch.Tenso
     _lib.call(vals.device, "srg_segment_sum_f64", seg_ptr.data_ptr(), vals.data_ptr() if vals.numel() else None,
               n_seg, out.data_ptr(), _lib.stream(vals.device))
     return out
+
+
+def row_sum_device(seg_ptr: torch.Tensor, vals: torch.Tensor) -> torch.Tensor:
+    """Row sums in the order of scipy's csr.sum(1) (srg_segment_sum_numpy_f64)."""
+    n_seg = seg_ptr.numel() - 1
+    out = torch.empty(n_seg, dtype=torch.float64, device=vals.device)
+    _lib.call(vals.device, "srg_segment_sum_numpy_f64", seg_ptr.data_ptr(),
+              vals.data_ptr() if vals.numel() else None, n_seg, out.data_ptr(), _lib.stream(vals.device))
+    return out
+
+
+def row_sum_host(seg_ptr: torch.Tensor, vals: torch.Tensor) -> torch.Tensor:
+    """The same sums for CPU tensors, through np.add.reduceat itself as scipy's _minor_reduce does."""
+    p, v = seg_ptr.numpy(), vals.numpy()
+    out = np.zeros(p.size - 1, dtype=np.float64)
+    full = np.flatnonzero(np.diff(p))
+    if full.size:
+        out[full] = np.add.reduceat(v, p[full])
+    return torch.from_numpy(out)
 
 
 def mirror_device(indptr: torch.Tensor, indices32: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
@@ -112,7 +140,8 @@ def _indptr(rows, n):
     return torch.searchsorted(rows, torch.arange(n + 1, dtype=rows.dtype, device=rows.device))
 
 
-def sym_norm(indptr, indices, data, n: int, r: float, device=None, segsum=None, mirror=None, fast=True):
+def sym_norm(indptr, indices, data, n: int, r: float, device=None, segsum=None, mirror=None, fast=True,
+             rowsum=None):
     """Â = D^(r-1) (A+I)^T D^(-r) of the CSR (indptr, indices, data) (host arrays or tensors).
     Returns device tensors (indptr int64, indices int32, values fp64), canonical CSR.
 
@@ -120,9 +149,12 @@ def sym_norm(indptr, indices, data, n: int, r: float, device=None, segsum=None, 
     gets A+I by merging the diagonals in place instead of a sort, and a structurally symmetric one
     (undirected graphs) its transpose from one binary search per entry (srg_csr_mirror) instead of
     a second sort -- the same values from the same fp64 operations, so the same bits; anything else
-    takes the general path."""
+    takes the general path.
+    segsum merges duplicates (sequential), rowsum gives the degrees (numpy's order); the defaults
+    are the device kernels, and for CPU tensors np.add.reduceat for the degrees."""
     segsum = segsum or segment_sum_device
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    rowsum = rowsum or (row_sum_device if dev.type == "cuda" else row_sum_host)
     # copy in the stored dtypes and widen on the device (a host-side int32 -> int64 conversion of
     # the column ids cost 0.24 s at products size)
     ip = torch.as_tensor(np.asarray(indptr) if not torch.is_tensor(indptr) else indptr).to(dev).to(torch.int64)
@@ -139,13 +171,16 @@ def sym_norm(indptr, indices, data, n: int, r: float, device=None, segsum=None, 
                                          torch.cat([v, torch.ones(n, dtype=torch.float64, device=dev)]), n, segsum)
         aip = _indptr(rows, n)
     del ip, ix, v
-    deg = segsum(aip, vals)
+    deg = rowsum(aip, vals)
     left, right = degree_powers(deg.cpu().numpy(), r)
     left_t = torch.from_numpy(left).to(dev)
     right_t = torch.from_numpy(right).to(dev)
+    # sp.diags stores no zero of left / right (a zero degree), so such a factor removes its entries
+    # whatever the product is (NaN * 0); without one, dropping the zero products is all there is
+    zero_factor = bool(((left_t == 0) | (right_t == 0)).any())
     if mirror is None and dev.type == "cuda":
         mirror = mirror_device
-    if fast and mirror is not None and vals.numel():
+    if fast and mirror is not None and vals.numel() and not zero_factor:
         cols32 = cols.to(torch.int32)
         m = mirror(aip, cols32, rows)
         if bool((m >= 0).all()):
@@ -156,18 +191,20 @@ def sym_norm(indptr, indices, data, n: int, r: float, device=None, segsum=None, 
         del m, cols32
     # stored (rows, cols) of A+I lands at (cols, rows) of Â
     step1 = vals * left_t[cols]
-    rows, cols, step1 = _kept(step1 != 0, rows, cols, step1)
+    keep = (step1 != 0) & (left_t != 0)[cols] if zero_factor else step1 != 0
+    rows, cols, step1 = _kept(keep, rows, cols, step1)
     step2 = step1 * right_t[rows]
-    t_cols, t_rows, step2 = _kept(step2 != 0, rows, cols, step2)
+    keep = (step2 != 0) & (right_t != 0)[rows] if zero_factor else step2 != 0
+    t_cols, t_rows, step2 = _kept(keep, rows, cols, step2)
     key, perm = torch.sort(t_rows * n + t_cols)
     return _indptr(key // n, n), (key % n).to(torch.int32), step2[perm]
 
 
 def ppr_norm(indptr, indices, data, n: int, r: float, alpha: float, device=None, segsum=None, mirror=None,
-             fast=True):
+             fast=True, rowsum=None):
     """(1 - alpha) Â + alpha I (symmetrical_simgraph_ppr_operator.py:19-21) on the device."""
     segsum = segsum or segment_sum_device
-    ip, ix, v = sym_norm(indptr, indices, data, n, r, device, segsum, mirror, fast)
+    ip, ix, v = sym_norm(indptr, indices, data, n, r, device, segsum, mirror, fast, rowsum)
     dev = ip.device
     rows = torch.repeat_interleave(torch.arange(n, device=dev), ip[1:] - ip[:-1])
     v = (1 - alpha) * v

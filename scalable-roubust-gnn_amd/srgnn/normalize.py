@@ -25,7 +25,7 @@ def degree_powers(deg: np.ndarray, r: float):
     right = np.empty_like(deg)
 
     def part(a, b):
-        with np.errstate(divide="ignore"):
+        with np.errstate(divide="ignore", invalid="ignore"):     # deg = 0 -> inf, deg < 0 -> NaN
             np.power(deg[a:b], r - 1, out=left[a:b])
             np.power(deg[a:b], -r, out=right[a:b])
 

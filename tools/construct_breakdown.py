@@ -40,7 +40,7 @@ diag = torch.arange(n, device=dev)
 r2, c2, v2 = t("canonical_sum(A+I)", lambda: C.canonical_sum(torch.cat([rows, diag]), torch.cat([ix, diag]),
                                                               torch.cat([vv, torch.ones(n, dtype=torch.float64, device=dev)]),
                                                               n, C.segment_sum_device))
-deg = t("degree_segsum", lambda: C.segment_sum_device(C._indptr(r2, n), v2))
+deg = t("degree_rowsum", lambda: C.row_sum_device(C._indptr(r2, n), v2))
 left, right = t("degree_powers(host)", lambda: C.degree_powers(deg.cpu().numpy(), 0.5))
 lt, rt = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)
 st = t("scale", lambda: (v2 * lt[c2]) * rt[r2])
