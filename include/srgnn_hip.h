@@ -542,6 +542,27 @@ int srg_spgemm_f32(int phase, const int64_t* a_ptr, const int32_t* a_idx, const 
                    const int64_t* b_ptr, const int32_t* b_idx, const float* b_val, int64_t n_cols,
                    int64_t* c_cnt, const int64_t* c_ptr, int32_t* c_idx, float* c_val, void* scratch,
                    int64_t scratch_bytes, uint32_t flags, void* stream);
+/* The adjoint of C = A * B (A: m x k, B: k x n, C's pattern as srg_spgemm_f32 emits it) with respect to
+ * the values of either operand, for G = dL/dC in C's entry order; one kernel serves both sides:
+ *   out[e] = ((0 + D[r, j1] * R[c, j1]) + D[r, j2] * R[c, j2]) + ...   for every entry e = (r, c) of a
+ * pattern P, over row c of R in stored order, every product rounded before it is added (no fma), from
+ * +0; D[r, j] is +0 where row r of D stores no entry (j1, j2, ... are row c of R's column ids).
+ *   dL/dA: P = A's pattern, D = G on C's CSR (m rows), R = B, n_cols = n:
+ *          gA[(i,k)] = sum over row k of B in stored order of G[i,j] * B[k,j];
+ *   dL/dB: P = B^T's pattern, D = G^T (n rows), R = A^T, n_cols = m, the transposes by a stable sort by
+ *          column: gB[(k,j)] = sum over A's entries in column k, rows ascending and duplicates in stored
+ *          order, of A[i,k] * G[i,j]; out is in B^T's entry order (the caller permutes it back).
+ * With R's rows column-sorted these are scipy csr_matmat's chains of G * B^T and A^T * G sampled at the
+ * patterns; duplicate entries of P each get the full value; an entry of C that the forward dropped (an
+ * exact-zero sum) is a +0 of D.  p_ptr and d_ptr have m + 1 entries; p_idx indexes R's rows; d_idx and
+ * r_idx are < n_cols; a row of D must not repeat a column id (R's and P's rows may).  out has one
+ * float per entry of P.  n_cols > 16384 needs `scratch` (device): srg_spgemm_scratch_bytes(m, n_cols)
+ * bytes are enough, any multiple of one accumulator (4 * n_cols bytes) does (fewer workgroups).  No
+ * atomics: run-to-run identical.  Non-finite inputs are undefined.  Asynchronous on `stream`. */
+int srg_spgemm_grad_f32(const int64_t* p_ptr, const int32_t* p_idx, int64_t m, const int64_t* d_ptr,
+                        const int32_t* d_idx, const float* d_val, const int64_t* r_ptr, const int32_t* r_idx,
+                        const float* r_val, int64_t n_cols, float* out, void* scratch, int64_t scratch_bytes,
+                        void* stream);
 /* torch_sparse.spmm(index, value, m, n, matrix) (index_select, mul, scatter_add): Y[r, :] = sum over
  * row r's entries in stored order of (v * X[c, :]), each product rounded, then added, from +0.  A CSR
  * whose rows hold the COO entries in index order (a stable sort by row). */

@@ -20,6 +20,10 @@
 //  * The touched words of the bitmap are scanned 64 at a time in ascending order; a wave prefix
 //    sum over the lanes' nonzero counts places each kept entry, so the columns come out sorted.
 //    The scan also resets what it read, leaving the accumulator zero for the workgroup's next row.
+//
+// The wavelet layers (wavelet/src/gwnn_layer.py) call spspmm with a learnable operand, so the product
+// has an adjoint here too: k_spgemm_grad, one kernel for dL/dA and dL/dB, each output one sequential
+// chain over a row of the other operand -- the forward's number of products, no fill-in.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -138,6 +142,50 @@ __global__ __launch_bounds__(64) void k_spgemm(const int64_t* __restrict__ ap, c
     }
 }
 
+// The adjoint of C = A * B for either operand (srgnn_hip.h): for every entry e of a pattern row r,
+//   out[e] = ((0 + D[r, j1] * R[k, j1]) + D[r, j2] * R[k, j2]) + ...   over row k = p_idx[e] of R in
+// stored order, every product rounded before it is added; D[r, j] is +0 where row r of D has no entry.
+// One workgroup per pattern row: row r of D is expanded into the dense accumulator the forward uses
+// (LDS up to kLdsCols columns, else the workgroup's slice of the scratch; no bitmap: the row's own
+// entries say what to reset), then each lane runs the whole chain of one pattern entry, so an output's
+// order of additions never depends on the schedule, and no two lanes write one word.
+constexpr int kGradThreads = 256;
+
+template <bool LDS>
+__global__ __launch_bounds__(kGradThreads) void k_spgemm_grad(
+    const int64_t* __restrict__ pp, const int32_t* __restrict__ pi, int64_t m, const int64_t* __restrict__ dp,
+    const int32_t* __restrict__ di, const float* __restrict__ dv, const int64_t* __restrict__ rp,
+    const int32_t* __restrict__ ri, const float* __restrict__ rv, int64_t ncols, float* __restrict__ out,
+    float* g_acc)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x;
+    float* acc;
+    if (LDS) {
+        acc = reinterpret_cast<float*>(smem);
+        for (int64_t i = tid; i < ncols; i += kGradThreads) acc[i] = 0.0f;
+    } else {
+        acc = g_acc + (int64_t)blockIdx.x * ncols;          // zero on entry (host memset), left zero
+    }
+    __syncthreads();
+    for (int64_t r = blockIdx.x; r < m; r += gridDim.x) {
+        const int64_t d0 = dp[r], d1 = dp[r + 1];
+        for (int64_t q = d0 + tid; q < d1; q += kGradThreads) acc[di[q]] = dv[q];
+        __syncthreads();
+        const int64_t e1 = pp[r + 1];
+        for (int64_t e = pp[r] + tid; e < e1; e += kGradThreads) {
+            const int32_t k = pi[e];
+            const int64_t q1 = rp[k + 1];
+            float s = 0.0f;
+            for (int64_t q = rp[k]; q < q1; ++q) s = __fadd_rn(s, __fmul_rn(acc[ri[q]], rv[q]));
+            out[e] = s;
+        }
+        __syncthreads();
+        for (int64_t q = d0 + tid; q < d1; q += kGradThreads) acc[di[q]] = 0.0f;
+        __syncthreads();
+    }
+}
+
 // Y[r, :] = sum over row r's entries, in stored order, of (v * X[c, :]) -- each product rounded,
 // then added, from +0: torch_sparse.spmm's index_select / mul / scatter_add arithmetic.
 __global__ __launch_bounds__(256) void k_spmm_muladd(const int64_t* __restrict__ ip, const int32_t* __restrict__ ix,
@@ -209,6 +257,40 @@ int srg_spgemm_f32(int phase, const int64_t* a_ptr, const int32_t* a_idx, const 
         SRG_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(grid * per), s));
         hipLaunchKernelGGL(k_spgemm<false>, dim3((unsigned)grid), dim3(kWave), 0, s, a_ptr, a_idx, a_val, m,
                            b_ptr, b_idx, b_val, n_cols, phase, c_cnt, c_ptr, c_idx, c_val, acc, bits, serial);
+    }
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_spgemm_grad_f32(const int64_t* p_ptr, const int32_t* p_idx, int64_t m, const int64_t* d_ptr,
+                        const int32_t* d_idx, const float* d_val, const int64_t* r_ptr, const int32_t* r_idx,
+                        const float* r_val, int64_t n_cols, float* out, void* scratch, int64_t scratch_bytes,
+                        void* stream)
+{
+    if (m < 0 || n_cols < 0 || n_cols > INT32_MAX) return srg_fail(SRG_ERR_INVALID, "bad shape m=%lld n=%lld",
+                                                                   (long long)m, (long long)n_cols);
+    if (m == 0) return srg_ok();
+    if (!p_ptr || !d_ptr || !r_ptr) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    SRG_DEVICE_GUARD(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_cols <= kLdsCols) {
+        const size_t lds = 4 * (size_t)((n_cols + 3) & ~int64_t(3));
+        if (lds > 48 * 1024)
+            SRG_HIP_CHECK(hipFuncSetAttribute((const void*)k_spgemm_grad<true>,
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const int64_t grid = m < kMaxGlobalSlots ? m : kMaxGlobalSlots;
+        hipLaunchKernelGGL(k_spgemm_grad<true>, dim3((unsigned)grid), dim3(kGradThreads), lds, s, p_ptr, p_idx, m,
+                           d_ptr, d_idx, d_val, r_ptr, r_idx, r_val, n_cols, out, (float*)nullptr);
+    } else {
+        const int64_t per = 4 * n_cols;
+        int64_t slots = scratch ? scratch_bytes / per : 0;
+        if (slots < 1) return srg_fail(SRG_ERR_INVALID, "scratch of %lld bytes < one accumulator (%lld)",
+                                       (long long)scratch_bytes, (long long)per);
+        if (slots > kMaxGlobalSlots) slots = kMaxGlobalSlots;
+        const int64_t grid = slots < m ? slots : m;
+        SRG_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(grid * per), s));
+        hipLaunchKernelGGL(k_spgemm_grad<false>, dim3((unsigned)grid), dim3(kGradThreads), 0, s, p_ptr, p_idx, m,
+                           d_ptr, d_idx, d_val, r_ptr, r_idx, r_val, n_cols, out, static_cast<float*>(scratch));
     }
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();

@@ -109,6 +109,7 @@ EXPORTED_SYMBOLS = (
     "srg_gather_rows_f32",
     "srg_spgemm_scratch_bytes",
     "srg_spgemm_f32",
+    "srg_spgemm_grad_f32",
     "srg_spmm_muladd_f32",
     "srg_hub_join",
     "srg_hub_side_streams",
@@ -226,6 +227,8 @@ def _declare(lib):
     lib.srg_spgemm_f32.argtypes = [ctypes.c_int, _p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64,
                                    _u32, _p]
     lib.srg_spgemm_f32.restype = ctypes.c_int
+    lib.srg_spgemm_grad_f32.argtypes = [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _p]
+    lib.srg_spgemm_grad_f32.restype = ctypes.c_int
     lib.srg_spmm_muladd_f32.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p]
     lib.srg_spmm_muladd_f32.restype = ctypes.c_int
     lib.srg_hub_join.argtypes = [_p]

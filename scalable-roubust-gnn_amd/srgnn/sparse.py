@@ -6,6 +6,9 @@ kernels have scipy csr_matmat's arithmetic, which is what libsrgnn_hip restates 
   * spgemm: C[i, j] = ((0 + A[i,k1] B[k1,j]) + A[i,k2] B[k2,j]) + ... over row i of A in stored
     order, every product rounded before it is added; zero sums dropped; columns ascending
     (srg_spgemm_f32: count pass, prefix sum, fill pass);
+  * spgemm_grad: the product's adjoint for either operand, one sequential chain per entry over a
+    row of the other operand in stored order (srg_spgemm_grad_f32); the B side runs on the
+    transposes csr_transpose builds (a stable sort by column);
   * spmm_scatter: Y[r] = ((0 + v1 X[c1]) + v2 X[c2]) + ... in the entries' order (index_select,
     mul, scatter_add; srg_spmm_muladd_f32).
 Parity: pinned against scipy's products of the same fp32 operands (bit for bit: scipy's
@@ -28,9 +31,11 @@ def _dev(t: torch.Tensor):
     return t.device
 
 
-def csr_from_coo(row: torch.Tensor, col: torch.Tensor, value: torch.Tensor, m: int, sort_cols: bool = False):
+def csr_from_coo(row: torch.Tensor, col: torch.Tensor, value: torch.Tensor, m: int, sort_cols: bool = False,
+                 return_perm: bool = False):
     """(indptr int64 [m+1], indices int32, values) with every row's entries in their COO order (a
-    stable sort by row; with sort_cols by (row, col)), on the tensors' device."""
+    stable sort by row; with sort_cols by (row, col)), on the tensors' device.  return_perm appends
+    the sort's permutation: CSR entry e is COO entry perm[e]."""
     row = row.to(torch.int64)
     col = col.to(torch.int64)
     if row.numel():
@@ -41,7 +46,17 @@ def csr_from_coo(row: torch.Tensor, col: torch.Tensor, value: torch.Tensor, m: i
     counts = torch.bincount(row, minlength=m) if row.numel() else torch.zeros(m, dtype=torch.int64, device=row.device)
     ip = torch.zeros(m + 1, dtype=torch.int64, device=row.device)
     torch.cumsum(counts, 0, out=ip[1:])
-    return ip, col[perm].to(torch.int32).contiguous(), value[perm].contiguous()
+    out = (ip, col[perm].to(torch.int32).contiguous(), value[perm].contiguous())
+    return out + (perm,) if return_perm else out
+
+
+def csr_transpose(ip: torch.Tensor, ix: torch.Tensor, v: torch.Tensor, n_cols: int):
+    """The transpose of a device CSR (rows x n_cols) as (indptr [n_cols + 1], indices, values, perm):
+    a stable sort of the entries by column, so a row of the transpose holds its entries with the
+    original rows ascending and equal (row, column) pairs in stored order.  Entry e of the
+    transpose is entry perm[e] of the operand."""
+    rows = torch.repeat_interleave(torch.arange(ip.numel() - 1, device=ip.device), ip[1:] - ip[:-1])
+    return csr_from_coo(ix, rows, v, int(n_cols), return_perm=True)
 
 
 def _rows_have_unique_cols(ip: torch.Tensor, ix: torch.Tensor, n_rows: int) -> bool:
@@ -111,6 +126,59 @@ def spgemm(a_ip, a_ix, a_v, b_ip, b_ix, b_v, n_cols: int, scratch_limit: int | N
     if nnz:
         run(1, c_ip.data_ptr(), c_ix.data_ptr(), c_v.data_ptr())
     return c_ip, c_ix, c_v
+
+
+def spgemm_grad(p_ip, p_ix, d_ip, d_ix, d_v, r_ip, r_ix, r_v, n_cols: int, scratch_limit: int | None = None,
+                check: bool = True) -> torch.Tensor:
+    """The adjoint of spgemm for one operand (srg_spgemm_grad_f32): for every entry e = (r, c) of the
+    pattern P, out[e] = ((0 + D[r,j1] R[c,j1]) + D[r,j2] R[c,j2]) + ... over row c of R in stored
+    order, each product rounded before it is added; D[r, j] = +0 where D stores nothing.
+      dL/dA of C = A @ B:  P = A, D = dL/dC on C's CSR, R = B, n_cols = B's columns;
+      dL/dB:               P = B^T, D = (dL/dC)^T, R = A^T (csr_transpose), n_cols = A's rows; the
+                           result is in B^T's entry order.
+    P and D have the same number of rows, P's column ids index R's rows, D's and R's are < n_cols,
+    and a row of D holds a column at most once.  check=False skips the checks that read the
+    operands back (for operands this module built itself)."""
+    dev = _dev(p_ip)
+    m, k = p_ip.numel() - 1, r_ip.numel() - 1
+    for t in (p_ix, d_ix, r_ix):
+        if t.dtype != torch.int32:
+            raise TypeError("column ids must be int32")
+    for t in (d_v, r_v):
+        if t.dtype != torch.float32:
+            raise TypeError(f"spgemm_grad computes in fp32, got {t.dtype}")
+    if d_ip.numel() - 1 != m:
+        raise ValueError(f"P has {m} rows, D {d_ip.numel() - 1}")
+    if check:
+        _check_csr(p_ip, p_ix, p_ix)                        # a pattern: no values
+        _check_csr(d_ip, d_ix, d_v)
+        _check_csr(r_ip, r_ix, r_v)
+        if p_ix.numel() and (int(p_ix.min()) < 0 or int(p_ix.max()) >= k):
+            raise ValueError("P's column ids must index R's rows")
+        for name, t in (("D", d_ix), ("R", r_ix)):
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n_cols):
+                raise ValueError(f"{name}'s column ids must be < {n_cols}")
+        if not _rows_have_unique_cols(d_ip, d_ix, m):
+            raise ValueError("a row of D repeats a column id")
+    p_ip, p_ix = p_ip.contiguous(), p_ix.contiguous()
+    d_ip, d_ix, d_v = d_ip.contiguous(), d_ix.contiguous(), d_v.contiguous()
+    r_ip, r_ix, r_v = r_ip.contiguous(), r_ix.contiguous(), r_v.contiguous()
+    need = ctypes.c_int64(0)
+    _lib.check(_lib.query("srg_spgemm_scratch_bytes", m, int(n_cols), ctypes.byref(need)), "srg_spgemm_scratch_bytes")
+    scratch = torch.empty(0, dtype=torch.uint8, device=dev)
+    if need.value:
+        free, _ = torch.cuda.mem_get_info(dev)
+        per = 4 * n_cols                                    # one accumulator; the adjoint keeps no bitmap
+        budget = min(need.value, scratch_limit if scratch_limit is not None else free // 4)
+        scratch = torch.empty(max(per, budget // per * per), dtype=torch.uint8, device=dev)
+    out = torch.empty(p_ix.numel(), dtype=torch.float32, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t.numel() else None
+    _lib.call(dev, "srg_spgemm_grad_f32", p_ip.data_ptr(), ptr(p_ix), m, d_ip.data_ptr(), ptr(d_ix), ptr(d_v),
+              r_ip.data_ptr(), ptr(r_ix), ptr(r_v), int(n_cols), ptr(out), ptr(scratch), scratch.numel(),
+              _lib.stream(dev))
+    return out
 
 
 def spmm_scatter(ip, ix, v, X: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:

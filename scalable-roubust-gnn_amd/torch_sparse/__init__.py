@@ -15,6 +15,16 @@ reference pins no version; these are the published torch_sparse 0.6.x semantics,
       which sorts without summing, whatever its docstring says: a1*b and a2*b are rounded and added
       separately).  Parity unpinned: torch_sparse is absent and the reference never passes it.
       -> srgnn.sparse.spgemm (srg_spgemm_f32).
+      Differentiable (once) in valueA and valueB, as the wavelet layers need (wavelet/src/gwnn_layer.py:
+      spspmm(phi, diag(theta)) then spspmm(., phi^-1) with theta a Parameter).  For G = dL/dvalue:
+        gA[(i,k)] = ((0 + G[i,j1] B[k,j1]) + G[i,j2] B[k,j2]) + ...   over row k of B in stored order,
+        gB[(k,j)] = ((0 + A[i1,k] G[i1,j]) + A[i2,k] G[i2,j]) + ...   over column k of A, rows
+                    ascending, duplicates in stored order,
+      products rounded before they are added, G = +0 at the exact-zero sums the forward dropped,
+      every duplicate entry getting the full value; with column-sorted rows that is scipy's
+      (G @ B.T) sampled at A's pattern and (A.T @ G) at B's.  Gradients arrive in the caller's entry
+      order on the caller's device; only the sides that require grad are computed.
+      -> srgnn.sparse.spgemm_grad (srg_spgemm_grad_f32).
   spmm(index, value, m, n, matrix) -> [m, ...] dense
       index_select, mul, scatter_add: each output row is the sum of its entries' rounded products in
       index order from 0 -> srgnn.sparse.spmm_scatter (srg_spmm_muladd_f32); differentiable in
@@ -29,6 +39,7 @@ Computation is fp32 (the reference passes torch.FloatTensor values).
 from __future__ import annotations
 
 import torch
+from torch.autograd.function import once_differentiable
 
 __version__ = "0.6.x-srgnn-hip"
 
@@ -45,28 +56,72 @@ def _on(t: torch.Tensor, dev):
     return t.to(dev) if t.device != dev else t
 
 
-def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False):
-    """Matrix product of two sparse tensors in COO form (torch_sparse 0.6.x `spspmm`)."""
+def _spspmm_csr(iA, vA, iB, vB, m, k, n, coalesced):
+    """The product of two device COO operands: (A's CSR + its sort's permutation, B's likewise,
+    C's CSR, C's COO index)."""
     from srgnn.sparse import csr_from_coo, spgemm
-    if torch.is_grad_enabled() and (getattr(valueA, "requires_grad", False) or getattr(valueB, "requires_grad", False)):
-        raise NotImplementedError("spspmm: gradients through the sparse product are outside the "
-                                  "preprocessing path this build covers (SpectralModel.preprocess)")
+    # coalesced=True: both inputs sorted by (row, col), duplicates kept in their stored order
+    # (torch_sparse 0.6.x: SparseTensor(row, col, value, is_sorted=not coalesced) sorts, never sums)
+    a = csr_from_coo(iA[0], iA[1], vA, m, sort_cols=coalesced, return_perm=True)
+    b = csr_from_coo(iB[0], iB[1], vB, k, sort_cols=coalesced, return_perm=True)
+    if a[1].numel() and int(a[1].max()) >= k:
+        raise ValueError(f"indexA has a column >= k = {k}")
+    c = spgemm(*a[:3], *b[:3], n)
+    rows = torch.repeat_interleave(torch.arange(m, device=vA.device), c[0][1:] - c[0][:-1])
+    return a, b, c, torch.stack([rows, c[1].to(torch.int64)], dim=0)
+
+
+class _SpSpMM(torch.autograd.Function):
+    """spspmm with the adjoint of srgnn.sparse.spgemm_grad; gradients in the caller's entry order."""
+
+    @staticmethod
+    def forward(ctx, indexA, valueA, indexB, valueB, m, k, n, coalesced):
+        a, b, c, index = _spspmm_csr(indexA, valueA.detach(), indexB, valueB.detach(), m, k, n, coalesced)
+        ctx.save_for_backward(*a, *b, c[0], c[1])
+        ctx.shape = (m, k, n)
+        ctx.mark_non_differentiable(index)
+        return index, c[2]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _grad_index, grad):
+        from srgnn.sparse import csr_transpose, spgemm_grad
+        a_ip, a_ix, a_v, a_perm, b_ip, b_ix, b_v, b_perm, c_ip, c_ix = ctx.saved_tensors
+        m, k, n = ctx.shape
+        g = grad.contiguous()
+        g_a = g_b = None
+        if ctx.needs_input_grad[1]:
+            # gA[(i,k)] = sum over row k of B of G[i,j] * B[k,j]; back from the row sort to the caller's order
+            g_a = torch.empty_like(a_v)
+            g_a[a_perm] = spgemm_grad(a_ip, a_ix, c_ip, c_ix, g, b_ip, b_ix, b_v, n, check=False)
+        if ctx.needs_input_grad[3]:
+            # gB[(k,j)] = sum over column k of A of A[i,k] * G[i,j]: the same kernel on the transposes
+            bt_ip, bt_ix, _, bt_perm = csr_transpose(b_ip, b_ix, b_v, n)
+            gt_ip, gt_ix, gt_v, _ = csr_transpose(c_ip, c_ix, g, n)
+            at_ip, at_ix, at_v, _ = csr_transpose(a_ip, a_ix, a_v, k)
+            g_csr = torch.empty_like(b_v)
+            g_csr[bt_perm] = spgemm_grad(bt_ip, bt_ix, gt_ip, gt_ix, gt_v, at_ip, at_ix, at_v, m, check=False)
+            g_b = torch.empty_like(b_v)
+            g_b[b_perm] = g_csr
+        return None, g_a, None, g_b, None, None, None, None
+
+
+def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False):
+    """Matrix product of two sparse tensors in COO form (torch_sparse 0.6.x `spspmm`); differentiable
+    (once) in valueA and valueB."""
     home = valueA.device
     dev = _device()
     iA, vA, iB, vB = (_on(t, dev) for t in (indexA, valueA, indexB, valueB))
     for v in (vA, vB):
         if v.dtype != torch.float32:
             raise TypeError(f"spspmm computes in float32, got {v.dtype}")
-    # coalesced=True: both inputs sorted by (row, col), duplicates kept in their stored order
-    # (torch_sparse 0.6.x: SparseTensor(row, col, value, is_sorted=not coalesced) sorts, never sums)
-    a = csr_from_coo(iA[0], iA[1], vA, int(m), sort_cols=bool(coalesced))
-    b = csr_from_coo(iB[0], iB[1], vB, int(k), sort_cols=bool(coalesced))
-    if a[1].numel() and int(a[1].max()) >= int(k):
-        raise ValueError(f"indexA has a column >= k = {k}")
-    c_ip, c_ix, c_v = spgemm(*a, *b, int(n))
-    rows = torch.repeat_interleave(torch.arange(int(m), device=dev), c_ip[1:] - c_ip[:-1])
-    index = torch.stack([rows, c_ix.to(torch.int64)], dim=0)
-    return index.to(home), c_v.to(home)
+    m, k, n, coalesced = int(m), int(k), int(n), bool(coalesced)
+    if torch.is_grad_enabled() and (vA.requires_grad or vB.requires_grad):
+        index, value = _SpSpMM.apply(iA, vA, iB, vB, m, k, n, coalesced)
+    else:
+        _, _, c, index = _spspmm_csr(iA, vA, iB, vB, m, k, n, coalesced)
+        value = c[2]
+    return index.to(home), value.to(home)
 
 
 class _SpMM(torch.autograd.Function):
