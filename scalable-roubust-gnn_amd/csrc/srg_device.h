@@ -1,0 +1,223 @@
+// srg_device.h -- device code that more than one kernel family uses: vector loads and stores, the chain
+// link and the epilogue arithmetic, the row-wave gather, the launch constants; and the host checks that go
+// with them.  Everything is in the anonymous namespace: each translation unit that includes this header
+// compiles its own copy into its own kernels.  Not part of the C-ABI (include/srgnn_hip.h).
+#ifndef SRG_DEVICE_H_
+#define SRG_DEVICE_H_
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "srgnn_hip.h"
+#include "srg_internal.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// vector helpers
+// ------------------------------------------------------------------------------------------------
+template <typename T, int VEC> struct Vec;
+template <> struct Vec<float, 1> { typedef float type; };
+template <> struct Vec<float, 2> { typedef float type __attribute__((ext_vector_type(2))); };
+template <> struct Vec<float, 4> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct Vec<double, 1> { typedef double type; };
+template <> struct Vec<double, 2> { typedef double type __attribute__((ext_vector_type(2))); };
+
+// element i of a scalar-or-vector value
+template <typename T> __device__ __forceinline__ T& elem(T& v, int) { return v; }
+template <typename T> __device__ __forceinline__ const T& elem(const T& v, int) { return v; }
+template <typename T, int N>
+__device__ __forceinline__ T& elem(T __attribute__((ext_vector_type(N)))& v, int i) { return reinterpret_cast<T*>(&v)[i]; }
+template <typename T, int N>
+__device__ __forceinline__ const T& elem(const T __attribute__((ext_vector_type(N)))& v, int i) { return reinterpret_cast<const T*>(&v)[i]; }
+
+template <typename T, int VEC>
+__device__ __forceinline__ typename Vec<T, VEC>::type vload(const T* p)
+{
+    return *reinterpret_cast<const typename Vec<T, VEC>::type*>(p);
+}
+// Gather of one X row piece (plain loads: the gathered rows are re-read from L2 / Infinity Cache;
+// non-temporal gathers measured 35 % slower on the products-shaped graph).
+template <typename T, int VEC>
+__device__ __forceinline__ typename Vec<T, VEC>::type gload(const T* p)
+{
+    return *reinterpret_cast<const typename Vec<T, VEC>::type*>(p);
+}
+
+template <typename T, int VEC>
+__device__ __forceinline__ void vstore(T* p, typename Vec<T, VEC>::type v, bool nt)
+{
+    typedef typename Vec<T, VEC>::type V;
+    if (nt)
+        __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
+    else
+        *reinterpret_cast<V*>(p) = v;
+}
+
+// One link of the reference chain: acc = fma(a, x, acc) per component (fp32), or acc + a*x without
+// contraction (fp64: scipy's csr_matvecs order, see srg_oracle.c).
+__device__ __forceinline__ float link(float a, float x, float acc) { return __builtin_fmaf(a, x, acc); }
+__device__ __forceinline__ double link(double a, double x, double acc)
+{
+    return __dadd_rn(acc, __dmul_rn(a, x));
+}
+
+// Epilogue arithmetic: fp64 follows numpy/scipy rounding exactly (no contraction into fma);
+// fp32 leaves the compiler free (the fp32 Chebyshev path is tolerance-checked).
+__device__ __forceinline__ double e_mul(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double e_add(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ double e_sub(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ double e_div(double a, double b) { return __ddiv_rn(a, b); }
+__device__ __forceinline__ float e_mul(float a, float b) { return a * b; }
+__device__ __forceinline__ float e_add(float a, float b) { return a + b; }
+__device__ __forceinline__ float e_sub(float a, float b) { return a - b; }
+__device__ __forceinline__ float e_div(float a, float b) { return a / b; }
+
+template <typename T, int VEC>
+__device__ __forceinline__ void chain(typename Vec<T, VEC>::type& acc, T a,
+                                      const typename Vec<T, VEC>::type& x)
+{
+    if constexpr (VEC == 1) {
+        acc = link(a, x, acc);
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc[i] = link(a, x[i], acc[i]);
+    }
+}
+
+template <typename T, int VEC> __device__ __forceinline__ typename Vec<T, VEC>::type vzero()
+{
+    typename Vec<T, VEC>::type z;
+    if constexpr (VEC == 1) {
+        z = T(0);
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) z[i] = T(0);
+    }
+    return z;
+}
+
+constexpr int kWavesPerBlock = 4;   // 256-thread workgroups
+constexpr int kBlock = 64 * kWavesPerBlock;
+
+// ------------------------------------------------------------------------------------------------
+// the row-wave gather: acc (+)= A[row, :] * X[:, col .. col+VEC)
+//
+// The row's (column id, value) stream is read 64 entries at a time with one coalesced vector load
+// (lane l holds entry jb + l), prefetched one block ahead, and broadcast to the whole wave with
+// v_readlane (the lane index is wave-uniform).  Each entry's X row address is then a scalar base
+// plus the lane's column offset.  U gathers are issued back to back, then consumed in CSR order.
+// Entries past the end of the row repeat its last entry and are skipped by a wave-uniform predicate
+// (never folded in as 0*x: that would flip -0.0 sums and turn inf/nan inputs into nan).
+// FULL: every lane of the wave owns columns (d is a multiple of 64*VEC), so no lane predicates.
+// ------------------------------------------------------------------------------------------------
+// SPAN: the row's entries end at row_end[row] instead of indptr[row + 1] (kEpiSpan, srg_spmm_kernels.h).
+template <typename T, int VEC, int U, bool FULL, typename IP, bool SPAN = false>
+__device__ __forceinline__ void row_gather(typename Vec<T, VEC>::type& acc,
+                                           const IP* __restrict__ indptr,
+                                           const int32_t* __restrict__ indices,
+                                           const T* __restrict__ vals, int row,
+                                           const T* __restrict__ X, int64_t ldx, int col, bool act,
+                                           const int64_t* __restrict__ row_end = nullptr)
+{
+    typedef typename Vec<T, VEC>::type V;
+    const int lane = threadIdx.x & 63;
+    const int64_t beg = indptr[row];
+    int64_t end;
+    if constexpr (SPAN)
+        end = row_end[row];
+    else
+        end = indptr[row + 1];
+    if (beg >= end) return;
+    // entries past the row end are clamped to its last entry (always a valid id; skipped below)
+    int64_t j0 = beg + lane;
+    j0 = j0 < end ? j0 : end - 1;
+    int c_nxt = indices[j0];
+    T a_nxt = vals[j0];
+    for (int64_t jb = beg; jb < end; jb += 64) {
+        const int c_blk = c_nxt;
+        const T a_blk = a_nxt;
+        int64_t jn = jb + 64 + lane;   // prefetch the next block of the stream
+        jn = jn < end ? jn : end - 1;
+        c_nxt = indices[jn];
+        a_nxt = vals[jn];
+        const int nblk = (end - jb) < 64 ? (int)(end - jb) : 64;   // wave-uniform
+        for (int s0 = 0; s0 < nblk; s0 += U) {
+            V x[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int c = __builtin_amdgcn_readlane(c_blk, s0 + u);
+                const T* p = X + (int64_t)c * ldx + col;
+                if (FULL || act)
+                    x[u] = gload<T, VEC>(p);
+                else
+                    x[u] = vzero<T, VEC>();
+            }
+            const int n = (nblk - s0) < U ? (nblk - s0) : U;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                T a;
+                if constexpr (sizeof(T) == 8) {   // v_readlane is 32-bit: broadcast both halves
+                    const unsigned long long bits = __builtin_bit_cast(unsigned long long, a_blk);
+                    const unsigned lo = __builtin_amdgcn_readlane((unsigned)bits, s0 + u);
+                    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(bits >> 32), s0 + u);
+                    a = __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
+                } else {
+                    a = __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a_blk), s0 + u));
+                }
+                if (u < n) chain<T, VEC>(acc, a, x[u]);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ int wave_slot(int block_base)
+{
+    // wave-uniform by construction; readfirstlane makes that provable to the compiler so that the
+    // row's index stream goes through the scalar path.
+    return __builtin_amdgcn_readfirstlane((int)((block_base + (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6)));
+}
+
+// A dispatch holds < 2^32 work-items per dimension: launches of more rows than that (111 M rows
+// of the papers100M-shaped graph = 7.1e9 lanes) go out in chunks of kMaxLaunchBlocks blocks, the
+// kernel adding the chunk's block_base to blockIdx.x.
+constexpr int64_t kMaxLaunchBlocks = int64_t(1) << 23;
+
+// ------------------------------------------------------------------------------------------------
+// launch helpers
+// ------------------------------------------------------------------------------------------------
+constexpr int kUnroll = 8;
+
+bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+int pick_vec(int d, int64_t ldx, int64_t ldy, const void* X, const void* Y, size_t elem)
+{
+    // widest per-lane access whose tiles line up with every row of X and Y
+    if (elem == 4 && d >= 256 && d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned(X, 16) &&
+        aligned(Y, 16))
+        return 4;
+    if (d >= 128 && d % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && aligned(X, 2 * elem) &&
+        aligned(Y, 2 * elem))
+        return 2;
+    return 1;
+}
+
+int check_spmm_args(const void* indptr, const void* indices, const void* vals, int64_t n_rows,
+                    const void* X, int64_t ldx, const void* Y, int64_t ldy, int d)
+{
+    if (n_rows < 0 || n_rows > INT32_MAX - 64)
+        return srg_fail(SRG_ERR_INVALID, "n_rows=%lld out of range [0, 2^31-64)", (long long)n_rows);
+    if (d < 0) return srg_fail(SRG_ERR_INVALID, "d=%d < 0", d);
+    if (ldx < d || ldy < d)
+        return srg_fail(SRG_ERR_INVALID, "leading dimensions (ldx=%lld, ldy=%lld) < d=%d",
+                        (long long)ldx, (long long)ldy, d);
+    if (n_rows > 0 && d > 0 && (!indptr || !Y))
+        return srg_fail(SRG_ERR_INVALID, "null indptr or Y");
+    (void)indices; (void)vals; (void)X;
+    return SRG_OK;
+}
+
+}  // namespace
+
+#endif  // SRG_DEVICE_H_

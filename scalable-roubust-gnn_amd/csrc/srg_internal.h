@@ -1,10 +1,13 @@
 // srg_internal.h -- host plumbing shared by every translation unit of the library: the thread-local
-// status behind srg_last_error, the HIP status check and the device guard of the entry points.  Defined
-// once, in srg_spmm.hip.  Not part of the C-ABI (include/srgnn_hip.h).
+// status behind srg_last_error, the HIP status check, the device guard of the entry points and the fork
+// of hub work onto a side stream.  Defined once, in srg_runtime.hip.  Not part of the C-ABI
+// (include/srgnn_hip.h).
 #ifndef SRG_INTERNAL_H_
 #define SRG_INTERNAL_H_
 
 #include <hip/hip_runtime.h>
+
+#include <mutex>
 
 #include "srgnn_hip.h"
 
@@ -36,6 +39,51 @@ struct DeviceGuard {
 #define SRG_DEVICE_GUARD(stream)                                   \
     DeviceGuard guard_(static_cast<hipStream_t>(stream));          \
     if (guard_.rc) return guard_.rc
+
+// The dynamic-LDS limits of one kernel family's hub kernels.  Kernel attributes are per device and the
+// kernels belong to the family's translation unit, so the family states how to raise them (`raise`, on
+// the current device) and HubFork::fork does so once per device, before the family's first hub launch
+// there, under the side-stream registry's lock (which also guards `done`).
+constexpr int kMaxDevices = 64;
+struct HubLds {
+    int (*raise)();
+    bool done[kMaxDevices];
+};
+
+struct SideStream;   // srg_runtime.hip: a (device, caller stream) entry of the registry
+
+// One launch's fork of hub work onto the side stream of (current device, caller stream), step by step:
+// fork, the hub launches on stream(), record_join, delay, the main launches, join.  Holds the registry's
+// lock from the first fork until it goes out of scope (the end of the launch: see SideStream), and makes
+// no HIP call when it does, so an error return only releases the lock.  A launch without hub rows never
+// forks and never takes the lock.
+class HubFork {
+public:
+    HubFork(hipStream_t caller, HubLds& lds);
+    // Orders the side stream after the caller's stream.  may_continue: when the entry has an unjoined
+    // fork, no new one is made (continued()): the hub work is appended to the side stream as it is.
+    // Forking again on one object forks again under the lock it already holds.
+    int fork(bool may_continue = false);
+    bool continued() const { return continued_; }
+    hipStream_t stream() const;
+    // After the hub launches; pending: the join is left to srg_hub_join.
+    int record_join(bool pending);
+    // The single-wave delay on the caller's stream (k_dispatch_delay)
+    int delay();
+    // The caller's stream waits for the recorded join (nothing to wait for without a fork).
+    int join();
+
+private:
+    hipStream_t s_;
+    HubLds& lds_;
+    std::unique_lock<std::mutex> lock_;
+    SideStream* ss_ = nullptr;
+    bool continued_ = false;
+};
+
+// Joins the side stream of (dev, s) into `s`: waits on the entry's join event -- only_pending: only after
+// an unjoined fork; otherwise whenever the entry has one -- and marks it joined.
+int join_side_stream(int dev, hipStream_t s, bool only_pending);
 
 #pragma GCC visibility pop
 

@@ -1,6 +1,7 @@
 // srg_plan_internal.h -- library-internal entry points between the one-GPU planner (srg_plan.hip: the
-// layout, its lifetime, the C-ABI over plans) and the kernels' translation unit (srg_spmm.hip: the
-// launch loops).  Not part of the C-ABI (include/srgnn_hip.h).
+// layout, its lifetime, the C-ABI over plans) and the kernels' translation units (the launch loops:
+// srg_spmm.hip for the fp32 hop, srg_cheby.hip for the fp64 Chebyshev step).  Not part of the C-ABI
+// (include/srgnn_hip.h).
 #ifndef SRG_PLAN_INTERNAL_H_
 #define SRG_PLAN_INTERNAL_H_
 

@@ -20,7 +20,7 @@ below says why); the fp32 arrays are float64 draws rounded once.
 
 Also here: the link-swap mutations the CPU tests hold the data to, the schedules the GPU tests run,
 and plain numpy references of the kernels' epilogues (one rounded operation at a time, in the working
-precision; the modes and operation order are those of cheby_epi_at's comment in csrc/srg_spmm.hip).
+precision; the modes and operation order are those of cheby_epi_at's comment in csrc/srg_cheby.hip).
 Test infrastructure only.
 """
 from __future__ import annotations

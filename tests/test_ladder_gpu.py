@@ -7,8 +7,10 @@ writes is a column window of a wider buffer filled with a sentinel; the whole bu
 the guard columns and the rows a launch does not schedule must come back untouched.  A failure names
 the first differing row, its length and column: with the schedule that locates the window or chunk.
 
-Which case reaches which instantiation (csrc/srg_spmm.hip; the device entries pass int64 row pointers,
-the int32 ones belong to the host drop-in entries and are not run here):
+Which case reaches which instantiation (the SpMM kernels of csrc/srg_spmm_kernels.h, instantiated with the
+plain and span epilogues by csrc/srg_spmm.hip and with the Chebyshev one by csrc/srg_cheby.hip, which also
+holds k_cheby*; the device entries pass int64 row pointers, the int32 ones belong to the host drop-in
+entries and are not run here):
 
   launch_spmm -> k_spmm, epilogue plain (test_csr_*), Chebyshev (test_spmm_cheby_f32: d = 32 narrow, 64
   packed, 100 one column per lane) and span (test_span_blocks_of_random_cuts: d = 32, 64, 128;

@@ -9,7 +9,7 @@
 // Hub rows are left out (the schedule passed starts after them).
 //   hipcc -O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -ffp-contract=off -Iinclude \
 //       tools/probes/xcd_probe.hip -o tools/probes/_build/libxcd_probe.so
-#include "../../scalable-roubust-gnn_amd/csrc/srg_spmm.hip"
+#include "../../scalable-roubust-gnn_amd/csrc/srg_spmm_kernels.h"
 
 namespace {
 
@@ -67,9 +67,9 @@ k_xprobe(const XBlk* __restrict__ blks, int mode, int fixed, int* __restrict__ c
 extern "C" int xprobe_run(const void* blks, int mode, int fixed, int* ctr, int* xlog, int grid, int n_slices,
                           const float* X, int64_t ldx, int d, void* stream)
 {
-    if (d != 128 || ldx % 4) return fail(SRG_ERR_INVALID, "probe is for d = 128");
+    // (the library's error state is not linked into the probe: plain status codes)
+    if (d != 128 || ldx % 4) return SRG_ERR_INVALID;   // the probe is for d = 128
     hipLaunchKernelGGL((k_xprobe<4, 2, 2>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
                        (const XBlk*)blks, mode, fixed, ctr, xlog, n_slices, X, ldx, d);
-    SRG_HIP_CHECK(hipGetLastError());
-    return SRG_OK;
+    return hipGetLastError() == hipSuccess ? SRG_OK : SRG_ERR_HIP;
 }
