@@ -45,7 +45,9 @@ extern "C" {
 /* ---- SpMM flags ------------------------------------------------------------------------------ */
 /* Default (0): every output element Y[i,c] is ONE sequential fp32 fma chain over row i's nonzeros
  * in stored CSR order, starting from +0.0f -- bit-identical to FloatCSRMulDenseOMP
- * (SSRG/operators/csrc/matmul.c:23-40) given a zeroed answer (SSRG/operators/utils.py:38). */
+ * (SSRG/operators/csrc/matmul.c:23-40) given a zeroed answer (SSRG/operators/utils.py:38).  Rows of X
+ * that row i does not reference never influence Y[i,:] (a NaN or Inf in them stays out), fp32 subnormals
+ * are kept, not flushed, and an empty row under SRG_SPMM_ACCUMULATE returns Y's bits unchanged. */
 #define SRG_SPMM_ACCUMULATE 0x1u   /* chains start from Y's current content (matmul.c contract) */
 #define SRG_SPMM_NT_STORE 0x2u     /* non-temporal stores of Y */
 /* Diagnostic: one light row per wave.  By default d <= 32 runs 64 / S rows per wave (S = the power

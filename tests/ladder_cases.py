@@ -18,10 +18,11 @@ treat differently, with data on which the order of a row's fma chain shows in th
 The fp64 variant is the same construction in float64 with the walk kept near 3 instead of 0 (WALK_CENTRE
 below says why); the fp32 arrays are float64 draws rounded once.
 
-Also here: the link-swap mutations the CPU tests hold the data to, the schedules the GPU tests run,
-and plain numpy references of the kernels' epilogues (one rounded operation at a time, in the working
-precision; the modes and operation order are those of cheby_epi_at's comment in csrc/srg_cheby.hip).
-Test infrastructure only.
+Also here: the special-value panels derived from that data (NaN, Inf, overflow, subnormals, a start
+panel of special words) with their NaN-aware comparison, the link-swap mutations the CPU tests hold
+the data to, the schedules the GPU tests run, and plain numpy references of the kernels' epilogues
+(one rounded operation at a time, in the working precision; the modes and operation order are those
+of cheby_epi_at's comment in csrc/srg_cheby.hip).  Test infrastructure only.
 """
 from __future__ import annotations
 
@@ -127,6 +128,84 @@ def side_panel(dtype, d, tag: int, rows=N) -> np.ndarray:
     """An O(1) signed panel [rows, d] for the operands beside the chain (Y to accumulate into, the
     aggregation panel, T_{k-1}, the scales' outputs): uniform in [-2, 2), seeded by (tag, d)."""
     return np.random.default_rng([SEED, 77, tag, d]).uniform(-2.0, 2.0, (rows, d)).astype(np_dtype(dtype))
+
+
+# ------------------------------------------------------------------------------------------------
+# special-value panels: what the finite O(1) data cannot show -- a lane without an entry folded into
+# the chain as 0 * X[0], a flushed subnormal, a chain that does not start from Y's own bits
+# ------------------------------------------------------------------------------------------------
+KINDS = ("poison", "inf", "overflow", "sub_deep", "sub_edge", "sub_x")
+QNAN = {"float32": 0x7FC00000, "float64": 0x7FF8000000000000}
+POISON_ROWS = (0, N - 1)     # row 0 is the id a lane without an entry gathers with
+# (log2 of the values' factor, log2 of X's): products and sums deep in the subnormal range; results on
+# both sides of FLT_MIN; a subnormal X under normal values
+SUB_SCALES = {"sub_deep": (-100, -40), "sub_edge": (-90, -37), "sub_x": (12, -140)}
+Y0_WORDS = (0x80000000, 0x00000000, 0x7FC01234, 0xFFC00001, 0x7F800000, 0xFF800000, 0x00000001, 0x807FFFFF)
+
+
+def uint_of(dtype):
+    return np.uint32 if np.dtype(dtype).itemsize == 4 else np.uint64
+
+
+def special(kind, dtype, d):
+    """(values, X) of one special-value case: the ladder operator's values and the gathered panel
+    [N, d], both in `dtype`.  The scaled kinds scale the float64 masters and round once."""
+    T = np_dtype(dtype)
+    centre = WALK_CENTRE[np.dtype(dtype).name]
+    if kind in SUB_SCALES:
+        sv, sx = SUB_SCALES[kind]
+        return (_walk(centre) * 2.0 ** sv).astype(T), np.ascontiguousarray(_x64()[:, :d] * 2.0 ** sx).astype(T)
+    v = operator(dtype)[2]
+    X = x_panel(dtype, d)
+    if kind == "poison":
+        X.view(uint_of(dtype))[list(POISON_ROWS)] = QNAN[np.dtype(dtype).name]
+    elif kind == "inf":
+        k = (31 * np.arange(N)[:, None] + 7 * np.arange(d)[None, :]) % 257
+        X[k == 0] = np.inf
+        X[k == 1] = -np.inf
+    elif kind == "overflow":
+        X *= T(2.0 ** 126)       # exact: X stays finite, the partial sums do not
+    else:
+        raise KeyError(kind)
+    return v, X
+
+
+def y0_special(d) -> np.ndarray:
+    """A [N, d] fp32 panel to accumulate into: element (r, c) is word (r + c) mod 8 of Y0_WORDS (-0, +0,
+    two quiet NaNs with payloads, +inf, -inf, the smallest and the largest negative subnormal)."""
+    words = np.array(Y0_WORDS, dtype=np.uint32)
+    return words[(np.arange(N)[:, None] + np.arange(d)[None, :]) % words.size].view(np.float32).copy()
+
+
+def poison_free_rows() -> np.ndarray:
+    """bool [N]: the rows that reference neither poisoned column."""
+    _, indices = structure()
+    hit = np.zeros(N, dtype=bool)
+    hit[np.repeat(np.arange(N), lengths())[np.isin(indices, POISON_ROWS)]] = True
+    return ~hit
+
+
+def special_diff(got, want, lens, sentinel, exact=None):
+    """The comparison for [N, ld] buffers that may hold NaN: None when they agree, else a message as
+    first_diff's.  Where the expected word is no NaN the bits must be equal; where it is a NaN the
+    result must be a NaN other than `sentinel` (payloads are not pinned: an invalid operation gives
+    0xFFC00000 on x86 and 0x7FC00000 on the GPU).  An expected sentinel (guard columns, rows a launch
+    does not schedule) must come back bit for bit, and so must every row of the bool [N] mask `exact`
+    (values a kernel only moves)."""
+    u = uint_of(got.dtype)
+    g, w = got.view(u), want.view(u)
+    free = np.isnan(want) & (w != u(sentinel))
+    if exact is not None:
+        free &= ~np.asarray(exact, dtype=bool)[:, None]
+    wrong = np.where(free, ~np.isnan(got) | (g == u(sentinel)), g != w)
+    bad = np.argwhere(wrong)
+    if not bad.size:
+        return None
+    r, c = (int(v) for v in bad[0])
+    rl = np.asarray(lens)[np.unique(bad[:, 0])]
+    return (f"{bad.shape[0]} elements of {rl.size} rows differ; first at row {r} (length {int(lens[r])}), "
+            f"buffer column {c}: got {got[r, c]!r} ({int(g[r, c]):#x}), want {want[r, c]!r} ({int(w[r, c]):#x}); "
+            f"lengths of the differing rows: {sorted(set(int(x) for x in rl))[:40]}")
 
 
 # ------------------------------------------------------------------------------------------------

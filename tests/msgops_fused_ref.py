@@ -112,3 +112,32 @@ def check_nafs(got, hops, what, against=None):
     print(f"nafs |got - exact| / bound  {what}: {worst:.4f}   (running max {max(_ratios.values()):.4f})")
     assert worst <= 1.0, f"{what}: {worst:.3f} of the bound"
     return worst
+
+
+# ------------------------------------------------------------------------------------------------
+# long hop lists through the weighted sum (test_aggregate_cpu.py, test_msgops_fused_gpu.py): torch's
+# multi_row_sum over the last n*d mod 32 elements takes its 16-row blocks from 64 terms on (16 per
+# interleaved partial sum) and its second level from 1024; combine_steps folds level 1 into level 2
+# from 256 terms on
+# ------------------------------------------------------------------------------------------------
+LONG_T = (64, 65, 255, 256, 257, 1024, 1027)
+LONG_SHAPES = ((5, 7), (2, 33), (3, 3))       # n*d = 35, 66, 9: tails of 3, 2 and all 9 elements
+LONG_ALPHA = 0.15                             # 0.15 * 0.85^k: an fp32 subnormal from term 526 on, zero from 629
+                                              # (an order-only case: those terms are swamped by terms 0 .. 525)
+
+
+def long_hops(n, d, T):
+    """T panels [n, d] as one [T, n, d] fp32 array, standard normal, seeded by the case."""
+    return np.random.default_rng([n, d, T]).standard_normal((T, n, d)).astype(np.float32)
+
+
+def long_hops_subnormal(n, d, T):
+    """long_hops scaled by 2^-135 (rounded once): every element, every product with a weight in [0.5, 1.5)
+    and every partial sum of up to 1,027 of them is an fp32 subnormal, so the result's bits are the
+    products' bits -- a step that flushes them returns zeros."""
+    return (long_hops(n, d, T).astype(np.float64) * 2.0 ** -135).astype(np.float32)
+
+
+def long_weights(T):
+    """T hand-crafted fp32 weights in [0.5, 1.5)."""
+    return np.random.default_rng([17, T]).uniform(0.5, 1.5, T).astype(np.float32)

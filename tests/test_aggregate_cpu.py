@@ -11,20 +11,26 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "scalable-roubust-gnn_amd"))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 
+import msgops_fused_ref as R  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from srgnn import aggregate as G  # noqa: E402
 
 f32 = np.float32
 
 
-def run_steps_np(steps, hops, n, d):
-    """numpy model of aggregate._DeviceSteps (INIT / ADD / fold / DIV / tail record / row_sum)."""
+def run_steps_np(steps, hops, n, d, flush=False):
+    """numpy model of aggregate._DeviceSteps (INIT / ADD / fold / DIV / tail record / row_sum).
+    flush: the model of a wrong build -- every subnormal product w * hop becomes zero."""
     slots, hist = {}, {}
     ts, tl = G.tail_range(n, d)
+    if flush:
+        tiny = np.finfo(f32).tiny
+        hops = [np.where(np.abs(h) < tiny, f32(0), h) for h in hops]       # a flushing multiply reads zeros too
+    keep = (lambda p: np.where(np.abs(p) < np.finfo(f32).tiny, f32(0), p).astype(f32)) if flush else (lambda p: p)
     for s in steps:
         if s[0] == "acc":
             _, slot, k, w = s
-            p = (f32(w) * hops[k]).astype(f32)
+            p = keep((f32(w) * hops[k]).astype(f32))
             slots[slot] = (slots.get(slot, np.zeros((n, d), f32)) + p).astype(f32)
         elif s[0] == "fold":
             _, dst, src = s
@@ -34,7 +40,7 @@ def run_steps_np(steps, hops, n, d):
             slots[0] = (slots.get(0, np.zeros((n, d), f32)) / f32(s[1])).astype(f32)
         elif s[0] == "tail":
             _, k, w, t = s
-            hist[t] = (f32(w) * hops[k].reshape(-1)[ts:ts + tl]).astype(f32)
+            hist[t] = keep((f32(w) * hops[k].reshape(-1)[ts:ts + tl]).astype(f32))
         elif s[0] == "rowsum":
             T = s[1]
             if tl == 0 or T == 0:
@@ -94,7 +100,7 @@ def _ref(msg, hops):
     return O.combine(msg.aggr_type, feats, msg.start, msg.end).numpy()
 
 
-def _fused_np(msg, hops):
+def _fused_np(msg, hops, flush=False):
     """Plan -> hop schedule (as propagate_aggregate consumes it) -> numpy execution."""
     mode, terms, div = G.combine_plan(msg, len(hops))
     if mode == "last":
@@ -107,7 +113,7 @@ def _fused_np(msg, hops):
     assert sorted(map(id, flat)) == sorted(map(id, steps))
     for k, g in enumerate(groups):
         assert all(G.step_hop(s) in (k, None) for s in g)
-    return run_steps_np(flat, hops, n, d)
+    return run_steps_np(flat, hops, n, d, flush)
 
 
 SHAPES = [(7, 1), (3, 3), (5, 7), (40, 33), (101, 13), (256, 128), (37, 500)]
@@ -151,6 +157,46 @@ def test_hand_crafted_weights():
         G.combine_plan(_Msg("learnable_weighted"), 5)
     with pytest.raises(ValueError):
         G.combine_plan(_Msg("sum", 4, 2), 5)
+
+
+@pytest.mark.parametrize("n,d", R.LONG_SHAPES)
+@pytest.mark.parametrize("T", R.LONG_T)
+def test_long_hop_lists_bit_exact(n, d, T):
+    """The planned order on lists long enough for multi_row_sum's 16-row blocks (T >= 64), the fold of
+    level 1 into level 2 (T >= 256) and multi_row_sum's own second level (T >= 1024): the numpy model
+    equals torch.  The twin of test_msgops_fused_gpu.py's device test, on its three cases:
+      hand-crafted weights in [0.5, 1.5) on O(1) panels;
+      alpha = 0.15 -- its weights run out (subnormal from term 526 on, zero from 629 on), but the terms
+        before them are O(0.1) and swamp those products: a case of the order alone;
+      the hand-crafted weights on panels scaled by 2^-135 -- every product and every sum is subnormal, so
+        a step that flushes them shows: the model with flushed products (run_steps_np's flush) differs
+        from torch in every element, and torch's own result is held to being unflushed."""
+    assert G.tail_range(n, d)[1] == {(5, 7): 3, (2, 33): 2, (3, 3): 9}[(n, d)]
+    hops = list(R.long_hops(n, d, T))
+    steps = G.combine_steps("weighted", [(k, 1.0) for k in range(T)])
+    assert (("fold", 2, 1) in steps) == (T >= 256)
+    crafted = _Msg("simple_weighted", 0, T, "hand_crafted", weight_list=torch.from_numpy(R.long_weights(T)))
+    for msg in (crafted, _Msg("simple_weighted", 0, T, "alpha", alpha=R.LONG_ALPHA)):
+        got, want = _fused_np(msg, hops), _ref(msg, hops)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{n}x{d} T={T} {msg.combination_type}"
+    tiny = np.finfo(f32).tiny
+    sub = R.long_hops_subnormal(n, d, T)
+    assert (np.abs(sub) < tiny).all() and (sub != 0).mean() > 0.999      # |x| < 2^-15 rounds to zero: 2.4e-5 of a normal draw
+    sub = list(sub)
+    got, want = _fused_np(crafted, sub), _ref(crafted, sub)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{n}x{d} T={T} subnormal panels"
+    assert ((want != 0) & (np.abs(want) < tiny)).all(), "the reference's sums are not nonzero subnormals"
+    flushed = _fused_np(crafted, sub, flush=True)
+    assert (flushed.view(np.uint32) != want.view(np.uint32)).all(), "flushed products would not show"
+
+
+def test_long_alpha_weights_run_out():
+    """The alpha case's fp32 weights are normal up to term 525, nonzero subnormals for terms 526 .. 628 and
+    zero from 629 on: lists of 1,024 and 1,027 terms carry subnormal and zero weights through the plan."""
+    _, terms, _ = G.combine_plan(_Msg("simple_weighted", 0, 1027, "alpha", alpha=R.LONG_ALPHA), 1027)
+    w = np.array([f32(w) for _, w in terms])
+    tiny = np.finfo(f32).tiny
+    assert (w[:526] >= tiny).all() and ((w[526:629] > 0) & (w[526:629] < tiny)).all() and not w[629:].any()
 
 
 def test_plan_shape():

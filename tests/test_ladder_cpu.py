@@ -1,6 +1,7 @@
 """The ladder operator (tests/ladder_cases.py) on the CPU: its generator's invariants, the condition
-that its data shows the order of a row's chain in the result bits, and the numpy epilogue references
-the GPU tests compare against (held to the oracle's own cheby_op).  No GPU."""
+that its data shows the order of a row's chain in the result bits, the numpy epilogue references the
+GPU tests compare against (held to the oracle's own cheby_op), and the conditions the special-value
+panels' references must meet for tests/test_ladder_special_gpu.py to mean something.  No GPU."""
 import numpy as np
 import pytest
 
@@ -198,3 +199,175 @@ def test_numpy_epilogues_round_every_operation():
     assert np.array_equal(LC.agg_ref(prev, 0.37, y), prev + (w * y))
     assert np.array_equal(LC.agg_ref(prev, 0.37, y, init=True), np.float32(0) + (w * y))
     assert LC.agg_ref(prev, 0.37, y).dtype == np.float32
+
+
+# ------------------------------------------------------------------------------------------------
+# the special-value panels: conditions the reference alone must meet, so that a host with
+# flush-to-zero set, or a changed ladder, cannot hollow the GPU tests out
+# ------------------------------------------------------------------------------------------------
+SPECIAL_D = [4, 32, 100, 256]
+TINY = float(np.finfo(np.float32).tiny)
+
+
+def _special_product(oracle_mod, kind, dtype, d):
+    ip, ix, _ = LC.operator(dtype)
+    v, X = LC.special(kind, dtype, d)
+    with np.errstate(all="ignore"):
+        y = oracle_mod.spmm(ip, ix, v, X) if dtype == "float32" else oracle_mod.spmm64(ip, ix, v, X)
+    return v, X, y
+
+
+def _subnormal(a):
+    return (a != 0) & (np.abs(a) < TINY)
+
+
+def test_special_builders_are_what_they_say():
+    d = 20
+    _, _, v = LC.operator("float32")
+    base = LC.x_panel("float32", d)
+    for kind in LC.KINDS:
+        a, b = LC.special(kind, "float32", d), LC.special(kind, "float32", d)
+        assert all(np.array_equal(p.view(np.uint32), q.view(np.uint32)) for p, q in zip(a, b)), kind
+        assert a[0].dtype == a[1].dtype == np.float32 and a[0].shape == v.shape and a[1].shape == (LC.N, d)
+        if kind not in LC.SUB_SCALES:
+            assert np.array_equal(a[0], v), kind
+    X = LC.special("poison", "float32", d)[1]
+    assert np.all(X.view(np.uint32)[[0, LC.N - 1]] == 0x7FC00000) and np.array_equal(X[1:-1], base[1:-1])
+    X64 = LC.special("poison", "float64", d)[1]
+    assert np.all(X64.view(np.uint64)[[0, LC.N - 1]] == 0x7FF8000000000000) and np.isfinite(X64[1:-1]).all()
+    X = LC.special("inf", "float32", d)[1]
+    k = (31 * np.arange(LC.N)[:, None] + 7 * np.arange(d)[None, :]) % 257
+    assert np.all(X[k == 0] == np.inf) and np.all(X[k == 1] == -np.inf) and np.array_equal(X[k > 1], base[k > 1])
+    assert (k == 0).sum() > 300 and (k == 1).sum() > 300
+    X = LC.special("overflow", "float32", d)[1]
+    assert np.isfinite(X).all() and np.array_equal(X.astype(np.float64), base.astype(np.float64) * 2.0 ** 126)
+    for kind, (sv, sx) in LC.SUB_SCALES.items():
+        vs, Xs = LC.special(kind, "float32", d)
+        assert np.array_equal(vs.astype(np.float64), v.astype(np.float64) * 2.0 ** sv), kind     # exact: normal
+        want = (LC._x64()[:, :d] * 2.0 ** sx).astype(np.float32)                               # rounded once
+        assert np.array_equal(Xs, want) and (Xs > 0).all(), kind
+    y0 = LC.y0_special(d).view(np.uint32)
+    assert y0.shape == (LC.N, d) and y0[0, 0] == 0x80000000 and y0[3, 4] == 0x807FFFFF and y0[5, 5] == 0x7FC01234
+    assert sorted(set(y0.ravel().tolist())) == sorted(LC.Y0_WORDS)
+    assert 0x7FC0DEAD not in LC.Y0_WORDS                # the GPU tests' unwritten-cell sentinel
+
+
+def test_special_diff_rules():
+    lens = np.array([3, 0, 5])
+    s = 0x7FC0DEAD
+    bits = lambda *w: np.array(w, dtype=np.uint32).view(np.float32).reshape(3, -1)      # noqa: E731
+    want = bits(0x3F800000, 0x7FC00000, 0x80000000, s, 0x7FC01234, 0x00000001)
+    assert LC.special_diff(want.copy(), want, lens, s) is None
+    # an expected NaN takes any NaN but the sentinel; payload and sign are free
+    assert LC.special_diff(bits(0x3F800000, 0xFFC00000, 0x80000000, s, 0x7FC00000, 0x00000001), want, lens, s) is None
+    assert "row 0 (length 3)" in LC.special_diff(bits(0x3F800000, s, 0x80000000, s, 0x7FC01234, 1), want, lens, s)
+    assert "row 0" in LC.special_diff(bits(0x3F800000, 0x7F800000, 0x80000000, s, 0x7FC01234, 1), want, lens, s)
+    # -0 is not +0, a flushed subnormal is seen, an overwritten sentinel is seen
+    assert "row 1 (length 0), buffer column 0" in LC.special_diff(bits(0x3F800000, 0x7FC00000, 0, s, 0x7FC01234, 1), want, lens, s)
+    assert "row 2 (length 5), buffer column 1" in LC.special_diff(bits(0x3F800000, 0x7FC00000, 0x80000000, s, 0x7FC01234, 0), want, lens, s)
+    assert "row 1" in LC.special_diff(bits(0x3F800000, 0x7FC00000, 0x80000000, 0x7FC00000, 0x7FC01234, 1), want, lens, s)
+    # rows marked exact keep their payloads
+    moved = bits(0x3F800000, 0x7FC00000, 0x80000000, s, 0x7FC00000, 1)
+    assert LC.special_diff(moved, want, lens, s, exact=[True, True, False]) is None
+    assert "row 2" in LC.special_diff(moved, want, lens, s, exact=[False, False, True])
+    w64 = np.array([[0x7FF8000000000000, 0x3FF0000000000000]], dtype=np.uint64).view(np.float64)
+    g64 = np.array([[0xFFF8000000000000, 0x3FF0000000000000]], dtype=np.uint64).view(np.float64)
+    assert LC.special_diff(g64, w64, np.array([1]), 0x7FF8DEADBEEF0BAD) is None
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_poison_reaches_only_the_rows_that_reference_it(oracle_mod, dtype):
+    """Rows that reference neither poisoned column are bitwise the unpoisoned reference, all other rows
+    NaN in every column; most rows -- of every role's lengths -- are clean, so a lane without an entry
+    that gathers X[0] into the chain shows.  Measured: 3,769 of 4,096 rows clean, 2,986 of the 3,024 rows
+    with at most 64 entries, 17 of the 54 rows longer than 1,064 (fp32 and fp64: the structure's)."""
+    lens = LC.lengths()
+    clean = LC.poison_free_rows()
+    u = LC.uint_of(dtype)
+    print(f"{dtype}: clean {clean.sum()} of {LC.N}; <= 64 entries {clean[lens <= 64].sum()} of {(lens <= 64).sum()}; "
+          f"> 1064 entries {clean[lens > 1064].sum()} of {(lens > 1064).sum()}")
+    assert clean.sum() >= 0.90 * LC.N
+    assert clean[lens <= 64].sum() >= 0.95 * (lens <= 64).sum()
+    assert clean[lens > 1064].sum() >= 10
+    assert clean[lens == 0].all()
+    for d in SPECIAL_D if dtype == "float32" else [16]:
+        ip, ix, v = LC.operator(dtype)
+        mul = oracle_mod.spmm if dtype == "float32" else oracle_mod.spmm64
+        base = mul(ip, ix, v, LC.x_panel(dtype, d))
+        _, _, y = _special_product(oracle_mod, "poison", dtype, d)
+        assert np.array_equal(y[clean].view(u), base[clean].view(u)), d
+        assert np.isnan(y[~clean]).all(), d
+
+
+@pytest.mark.parametrize("d", SPECIAL_D)
+def test_subnormal_panels_stay_subnormal(oracle_mod, d):
+    """Measured over d = 4, 32, 100, 256: sub_deep 99.94 - 99.96 % of the elements of non-empty rows nonzero
+    subnormals; sub_edge 85 - 89 % subnormal and 11 - 15 % normal; sub_x every X element subnormal and
+    98.7 - 99.2 % of the results subnormal.  A host that flushes subnormals gives 0 % everywhere."""
+    ne = LC.lengths() > 0
+    _, X, y = _special_product(oracle_mod, "sub_deep", "float32", d)
+    share = _subnormal(y[ne]).mean()
+    print(f"d={d} sub_deep: subnormal {100 * share:.2f} %")
+    assert np.isfinite(y).all() and share >= 0.99 and not y[~ne].any()
+    _, X, y = _special_product(oracle_mod, "sub_edge", "float32", d)
+    sub, normal = _subnormal(y[ne]).mean(), (np.abs(y[ne]) >= TINY).mean()
+    print(f"d={d} sub_edge: subnormal {100 * sub:.2f} %, normal {100 * normal:.2f} %")
+    assert np.isfinite(y).all() and sub >= 0.05 and normal >= 0.05
+    v, X, y = _special_product(oracle_mod, "sub_x", "float32", d)
+    share = _subnormal(y[ne]).mean()
+    print(f"d={d} sub_x: subnormal {100 * share:.2f} %")
+    assert _subnormal(X).all() and (np.abs(v) >= TINY).all() and np.isfinite(y).all() and share >= 0.95
+
+
+@pytest.mark.parametrize("d", SPECIAL_D)
+def test_inf_and_overflow_panels_mix_their_classes(oracle_mod, d):
+    """Measured: inf about 60 / 20 / 20 % finite / infinite / NaN results; overflow 6.8 - 10.3 % infinite
+    results from a finite X and no NaN (a partial sum that crossed FLT_MAX stays infinite with its sign:
+    which elements are infinite depends on the chain's order)."""
+    _, X, y = _special_product(oracle_mod, "inf", "float32", d)
+    fin, inf, nan = np.isfinite(y).mean(), np.isinf(y).mean(), np.isnan(y).mean()
+    print(f"d={d} inf: finite {100 * fin:.1f} %, infinite {100 * inf:.1f} %, NaN {100 * nan:.1f} %")
+    assert min(fin, inf, nan) >= 0.10
+    _, X, y = _special_product(oracle_mod, "overflow", "float32", d)
+    inf = np.isinf(y).mean()
+    print(f"d={d} overflow: infinite {100 * inf:.2f} %")
+    assert np.isfinite(X).all() and 0.03 <= inf <= 0.30 and not np.isnan(y).any()
+
+
+@pytest.mark.parametrize("d", SPECIAL_D)
+def test_accumulate_from_special_words(oracle_mod, d):
+    """ACCUMULATE from y0_special: the 47 empty rows come back bit for bit (payloads and -0 included),
+    every NaN the start holds is a NaN in the result, and -- sub_deep on that start -- the chains that
+    start from a subnormal, a zero of either sign or an infinity stay what IEEE makes of them."""
+    ip, ix, v = LC.operator("float32")
+    lens = LC.lengths()
+    y0 = LC.y0_special(d)
+    empty = lens == 0
+    assert empty.sum() == 47
+    for kind in (None, "sub_deep"):
+        vals, X = (v, LC.x_panel("float32", d)) if kind is None else LC.special(kind, "float32", d)
+        y = oracle_mod.spmm(ip, ix, vals, X, out=y0.copy(), accumulate=True)
+        assert np.array_equal(y[empty].view(np.uint32), y0[empty].view(np.uint32)), kind
+        assert np.isnan(y[np.isnan(y0)]).all() and np.array_equal(np.isinf(y), np.isinf(y0)), kind
+    # the last y is sub_deep's: from +-0 or the smallest subnormal the result is a nonzero subnormal (as
+    # 99.9 % of sub_deep's own results are); from the largest negative subnormal a negative sum ends normal
+    tiny0 = (np.abs(y0) <= np.float32(2.0 ** -149)) & ~empty[:, None]
+    share = _subnormal(y[tiny0]).mean()
+    edge = (y0.view(np.uint32) == 0x807FFFFF) & ~empty[:, None]
+    sub, normal = _subnormal(y[edge]).mean(), (np.abs(y[edge]) >= TINY).mean()
+    print(f"d={d} sub_deep from y0_special: {100 * share:.2f} % of the chains from +-0 / 2^-149 end subnormal; "
+          f"from -(2^-126 - 2^-149): {100 * sub:.1f} % subnormal, {100 * normal:.1f} % normal")
+    assert share >= 0.99 and sub >= 0.25 and normal >= 0.25
+
+
+@pytest.mark.parametrize("d", [32, 64, 100])
+def test_aggregation_weight_keeps_the_products_subnormal(oracle_mod, d):
+    """The aggregation epilogue's product w * acc on sub_deep: acc is a multiple of 2^-149 of magnitude up
+    to a few thousand units, so 0.37 acc rounds to zero only for |acc| of one unit: at least 99 % of the
+    products of non-empty rows are nonzero subnormals, and the sums with y0_special's tiny words are too."""
+    ne = LC.lengths() > 0
+    _, _, y = _special_product(oracle_mod, "sub_deep", "float32", d)
+    p = LC.agg_ref(None, 0.37, y, init=True)
+    share = _subnormal(p[ne]).mean()
+    print(f"d={d}: {100 * share:.2f} % of 0.37 acc nonzero subnormals")
+    assert share >= 0.99

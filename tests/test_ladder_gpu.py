@@ -375,13 +375,13 @@ def test_planned_hop(oracle_mod, d, col_blocks, agg):
 # ------------------------------------------------------------------------------------------------
 # the Chebyshev entries
 # ------------------------------------------------------------------------------------------------
-def cheby_case(oracle, dtype, d, mode, ns, rows, alias=False):
+def cheby_case(oracle, dtype, d, mode, ns, rows, alias=False, acc=None, tc=None):
     """The operands and the expected buffers of one step over the ladder operator: acc = A Tc is the
     oracle's, the epilogue numpy's.  Returns (Tc, To, Tn, R panels, expected Tn buffer, expected R buffer,
-    coef_prev, coef)."""
+    coef_prev, coef).  acc, tc: another gathered panel and its product (the special-value cases)."""
     m = mode & 0xF
-    acc = product(oracle, dtype, d)
-    tc = LC.x_panel(dtype, d)
+    if acc is None:
+        acc, tc = product(oracle, dtype, d), LC.x_panel(dtype, d)
     to = LC.side_panel(dtype, d, 5)
     r0 = np.stack([LC.side_panel(dtype, d, 6 + s) for s in range(ns)])
     cp = None

@@ -178,6 +178,33 @@ def test_combine_device_every_operator():
         combine_device(SumMessageOp(0, 5), dev[:2] + [dev[2][:, :3]])
 
 
+@pytest.mark.parametrize("n,d", R.LONG_SHAPES)
+@pytest.mark.parametrize("T", R.LONG_T)
+def test_combine_device_long_hop_lists(oracle_mod, n, d, T):
+    """The weighted sum over 64 to 1,027 held panels: k_tail_rowsum's 16-row block loop (T >= 64) and its
+    second level (T >= 1024), the ("fold", 2, 1) steps (T >= 256).  Three cases: hand-crafted weights on
+    O(1) panels; alpha = 0.15, whose weights are subnormal from term 526 on and zero from 629 on (the order
+    alone: terms 0 .. 525 swamp those products); and the hand-crafted weights on panels scaled by 2^-135,
+    where every product and sum is an fp32 subnormal -- that one holds k_hop_accumulate, k_tail_record and
+    k_tail_rowsum to unflushed arithmetic (flushed products change every element of the expected result:
+    test_aggregate_cpu.py::test_long_hop_lists_bit_exact).  Against oracle.combine (the reference's own
+    torch CPU operation), bit for bit; the planned order alone equals it on the CPU (the same test)."""
+    from operators.message_operator.simple_weighted_message_op import SimpleWeightedMessageOp
+    from srgnn.aggregate import combine_device, tail_range
+    w = torch.from_numpy(R.long_weights(T))
+    crafted, kw = SimpleWeightedMessageOp(0, T, "hand_crafted", w), dict(weight_list=w)
+    plain, sub = R.long_hops(n, d, T), R.long_hops_subnormal(n, d, T)
+    for what, hops, op, kw in (("hand_crafted", plain, crafted, kw),
+                               ("alpha", plain, SimpleWeightedMessageOp(0, T, "alpha", R.LONG_ALPHA), dict(alpha=R.LONG_ALPHA)),
+                               ("subnormal panels", sub, crafted, kw)):
+        want = oracle_mod.combine("simple_weighted", [torch.from_numpy(h) for h in hops], 0, T, **kw).numpy()
+        got = combine_device(op, list(torch.from_numpy(hops).cuda())).cpu().numpy()
+        diff = np.flatnonzero(R.bits(got).ravel() != R.bits(want).ravel())
+        assert diff.size == 0, (f"{n}x{d} T={T} {what}: {diff.size} elements differ, first flat element {diff[0]} "
+                                f"(the tail starts at {tail_range(n, d)[0]}): got {got.ravel()[diff[0]]!r}, "
+                                f"want {want.ravel()[diff[0]]!r}")
+
+
 def _select_ops(K):
     ops = [_Msg("min", 0, K + 1), _Msg("min", 1, K), _Msg("max", 0, K + 1), _Msg("max", 2, None),
            _Msg("concat", 0, K + 1), _Msg("concat", 1, K + 1), _Msg("concat", None, None)]
