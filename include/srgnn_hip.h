@@ -570,6 +570,22 @@ int srg_spgemm_grad_f32(const int64_t* p_ptr, const int32_t* p_idx, int64_t m, c
  * whose rows hold the COO entries in index order (a stable sort by row). */
 int srg_spmm_muladd_f32(const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows,
                         const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d, void* stream);
+/* The sampled dense-dense product (SDDMM): torch_sparse.spmm's gradient with respect to `value`.  For
+ * every entry e = (r, c) of a CSR pattern (indptr: int64 [n_rows + 1] from 0 to nnz; indices: int32 [nnz],
+ * rows of X) and panels G [n_rows, d] (row stride ldg) and X [., d] (row stride ldx), both strides in
+ * elements and >= d (column windows of wider panels are fine):
+ *   out[e] = ((((+0 + G[r,0]*X[c,0]) + G[r,1]*X[c,1]) + ...) + G[r,d-1]*X[c,d-1]),
+ * columns ascending from +0, every product rounded to fp32 before it is added (no fma); d == 0 writes +0.
+ * NaN, +-Inf, -0 and subnormals follow IEEE through this chain (nothing is flushed).  Duplicate entries
+ * each get the full value.  perm (int64 [nnz], a permutation) may be NULL; if given, entry e's result
+ * goes to out[perm[e]] (the caller's COO order, with perm the row sort's permutation), else to out[e].
+ * nnz is passed because the host cannot read indptr[n_rows]; the pattern is trusted.  One lane runs one
+ * entry's whole chain and nothing is added atomically: run-to-run identical, and the same bits whether
+ * the aligned (16-byte loads) or the unaligned path runs.  n_rows == 0 or nnz == 0 is a no-op.
+ * Asynchronous on `stream`. */
+int srg_sddmm_f32(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const float* G,
+                  int64_t ldg, const float* X, int64_t ldx, int32_t d, const int64_t* perm, float* out,
+                  void* stream);
 
 /* ---- multi-GPU: communicators and the row-partitioned K-hop propagation ---------------------------
  * SURVEY.md §8(b) item 5, for C / C++ hosts (the Python package drives the same kernels through

@@ -29,6 +29,7 @@
 #include <climits>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "srg_internal.h"
 #include "srgnn_hip.h"
@@ -206,6 +207,106 @@ __global__ __launch_bounds__(256) void k_spmm_muladd(const int64_t* __restrict__
     }
 }
 
+// The sampled dense-dense product (srgnn_hip.h: srg_sddmm_f32; spmm's value gradient): for entry
+// e = (r, c), out[e] = ((+0 + G[r,0]*X[c,0]) + G[r,1]*X[c,1]) + ..., every product rounded before it is
+// added, columns ascending.  One lane per entry -- a chain cannot be split across lanes without changing
+// its order -- and one wave (= one workgroup) per 64 consecutive CSR entries, each lane finding its row by
+// an upper-bound search over indptr, so long rows and short rows load the lanes alike.
+//  * X's 64 gathered rows are staged kSdTile columns at a time into the wave's LDS tile with coalesced
+//    loads (VEC: 16 bytes per lane, 8 lanes per row, 8 rows per instruction; otherwise 4 bytes per lane,
+//    32 lanes per row), kSdLd = kSdTile + 4 dwords per row: lane l then reads its own row as 16-byte
+//    pieces at dword l * 36 + j, 16-byte slot (9 l + j / 4) mod 16 -- distinct over each of
+//    ds_read_b128's 16-lane groups (their lane ids are distinct mod 16 and 9 is odd): no bank conflict.
+//  * The next tile's loads are issued into registers before the current tile's chain runs and stored to
+//    LDS after it.
+//  * G is read by each lane from its own row; lanes of one row read one address (one request).
+//  * VEC needs 16-byte aligned bases and strides that are multiples of 4; it stages d & ~3 columns and
+//    takes the last d & 3 columns straight from memory.  Either path runs the same chain: same bits.
+typedef float f32x4 __attribute__((ext_vector_type(4)));    // stays in registers as an array element
+constexpr int kSdTile = 32;
+constexpr int kSdLd = kSdTile + 4;
+
+template <bool VEC>
+__global__ __launch_bounds__(kWave) void k_sddmm(const int64_t* __restrict__ ip, const int32_t* __restrict__ ix,
+                                                 int64_t n_rows, int64_t e0, int64_t nnz,
+                                                 const float* __restrict__ G, int64_t ldg,
+                                                 const float* __restrict__ X, int64_t ldx, int d,
+                                                 const int64_t* __restrict__ perm, float* __restrict__ out)
+{
+    __shared__ __align__(16) float tile[kWave * kSdLd];
+    constexpr int kRegs = VEC ? kSdTile / 4 : kSdTile;      // staging registers: 8 float4 or 32 floats
+    const int lane = threadIdx.x;
+    const int64_t e = e0 + (int64_t)blockIdx.x * kWave + lane;
+    const bool live = e < nnz;
+    int64_t r = 0;
+    int32_t c = 0;
+    if (live && d > 0) {
+        int64_t lo = 1, hi = n_rows;                        // the first i in [1, n_rows] with ip[i] > e
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (ip[mid] > e) hi = mid; else lo = mid + 1;
+        }
+        r = lo - 1;
+        c = ix[e];
+    }
+    r = live ? r : __shfl(r, 0, kWave);                     // lane 0 is live: idle lanes redo its entry
+    c = live ? c : __shfl(c, 0, kWave);
+    const float* g = G + r * ldg;
+    const int dt = VEC ? (d & ~3) : d;                      // columns that go through the LDS tile
+    using Piece = std::conditional_t<VEC, f32x4, float>;
+    Piece v[kRegs];
+
+    // the 64 rows' columns [c0, c0 + w) into the staging registers: coalesced along each row
+    auto fetch = [&](int c0, int w) {
+#pragma unroll
+        for (int i = 0; i < kRegs; ++i) {
+            const int row = VEC ? i * 8 + (lane >> 3) : i * 2 + (lane >> 5);
+            const int col = VEC ? (lane & 7) * 4 : lane & 31;
+            const int32_t cr = __shfl(c, row, kWave);
+            // past the tile's width a lane loads its row's first piece again (every register is written)
+            v[i] = *reinterpret_cast<const Piece*>(X + (int64_t)cr * ldx + c0 + (col < w ? col : 0));
+        }
+    };
+    auto stage = [&](int w) {
+#pragma unroll
+        for (int i = 0; i < kRegs; ++i) {
+            const int row = VEC ? i * 8 + (lane >> 3) : i * 2 + (lane >> 5);
+            const int col = VEC ? (lane & 7) * 4 : lane & 31;
+            if (col < w) *reinterpret_cast<Piece*>(&tile[row * kSdLd + col]) = v[i];
+        }
+    };
+
+    float s = 0.0f;
+    if (dt > 0) fetch(0, dt < kSdTile ? dt : kSdTile);
+    for (int c0 = 0; c0 < dt; c0 += kSdTile) {
+        const int w = dt - c0 < kSdTile ? dt - c0 : kSdTile;
+        __syncthreads();                                    // the previous tile has been read
+        stage(w);
+        __syncthreads();
+        const int c1 = c0 + kSdTile;
+        if (c1 < dt) fetch(c1, dt - c1 < kSdTile ? dt - c1 : kSdTile);
+        const float* mine = &tile[lane * kSdLd];
+        for (int j = 0; j < w; j += 4) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(mine + j);
+            if (VEC) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(g + c0 + j);
+                s = __fadd_rn(s, __fmul_rn(a.x, x.x));
+                s = __fadd_rn(s, __fmul_rn(a.y, x.y));
+                s = __fadd_rn(s, __fmul_rn(a.z, x.z));
+                s = __fadd_rn(s, __fmul_rn(a.w, x.w));
+            } else {
+                const float xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (j + k < w) s = __fadd_rn(s, __fmul_rn(g[c0 + j + k], xs[k]));
+            }
+        }
+    }
+    const float* x = X + (int64_t)c * ldx;
+    for (int j = dt; j < d; ++j) s = __fadd_rn(s, __fmul_rn(g[j], x[j]));     // VEC: the last d & 3 columns
+    if (live) out[perm ? perm[e] : e] = s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -309,6 +410,35 @@ int srg_spmm_muladd_f32(const int64_t* indptr, const int32_t* indices, const flo
         const int64_t r0 = b0 * 4;
         hipLaunchKernelGGL(k_spmm_muladd, dim3((unsigned)nb), dim3(256), 0, static_cast<hipStream_t>(stream),
                            indptr + r0, indices, values, n_rows - r0, X, ldx, Y + r0 * ldy, ldy, d);
+    }
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_sddmm_f32(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const float* G,
+                  int64_t ldg, const float* X, int64_t ldx, int32_t d, const int64_t* perm, float* out,
+                  void* stream)
+{
+    if (n_rows < 0 || nnz < 0 || d < 0)
+        return srg_fail(SRG_ERR_INVALID, "bad shape n_rows=%lld nnz=%lld d=%d", (long long)n_rows, (long long)nnz,
+                        (int)d);
+    if (ldg < d || ldx < d)
+        return srg_fail(SRG_ERR_INVALID, "row stride ldg=%lld or ldx=%lld < d=%d", (long long)ldg, (long long)ldx,
+                        (int)d);
+    if (n_rows == 0 || nnz == 0) return srg_ok();
+    if (!out || (d > 0 && (!indptr || !indices || !G || !X))) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    SRG_DEVICE_GUARD(stream);
+    const bool vec = ((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(X)) & 15) == 0 &&
+                     ldg % 4 == 0 && ldx % 4 == 0;
+    const int64_t blocks = (nnz + kWave - 1) / kWave;
+    for (int64_t b0 = 0; b0 < blocks; b0 += (int64_t)1 << 24) {     // < 2^31 work-items per launch
+        const int64_t nb = blocks - b0 < ((int64_t)1 << 24) ? blocks - b0 : ((int64_t)1 << 24);
+        if (vec)
+            hipLaunchKernelGGL(k_sddmm<true>, dim3((unsigned)nb), dim3(kWave), 0, static_cast<hipStream_t>(stream),
+                               indptr, indices, n_rows, b0 * kWave, nnz, G, ldg, X, ldx, d, perm, out);
+        else
+            hipLaunchKernelGGL(k_sddmm<false>, dim3((unsigned)nb), dim3(kWave), 0, static_cast<hipStream_t>(stream),
+                               indptr, indices, n_rows, b0 * kWave, nnz, G, ldg, X, ldx, d, perm, out);
     }
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();

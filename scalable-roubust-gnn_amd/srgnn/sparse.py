@@ -10,7 +10,11 @@ kernels have scipy csr_matmat's arithmetic, which is what libsrgnn_hip restates 
     row of the other operand in stored order (srg_spgemm_grad_f32); the B side runs on the
     transposes csr_transpose builds (a stable sort by column);
   * spmm_scatter: Y[r] = ((0 + v1 X[c1]) + v2 X[c2]) + ... in the entries' order (index_select,
-    mul, scatter_add; srg_spmm_muladd_f32).
+    mul, scatter_add; srg_spmm_muladd_f32);
+  * sddmm: spmm's gradient with respect to its values, out[(r, c)] = ((0 + G[r,0] X[c,0]) +
+    G[r,1] X[c,1]) + ... over the columns ascending, one sequential chain per entry (srg_sddmm_f32);
+    the reference's own path (torch's vectorised sum) has no single order, so this one is pinned by
+    its host restatement (tests/sddmm_ref.py) and a derived rounding bound.
 Parity: pinned against scipy's products of the same fp32 operands (bit for bit: scipy's
 csr_matmat and csr_matvecs use the same separately rounded multiply-add in the same order) and
 against the wavelet fixtures' processed_feature (tests/golden/wav_*.npz, whose torch_sparse
@@ -202,4 +206,63 @@ def spmm_scatter(ip, ix, v, X: torch.Tensor, out: torch.Tensor | None = None) ->
     _lib.call(dev, "srg_spmm_muladd_f32", ip.data_ptr(), ix.data_ptr() if ix.numel() else None,
               v.data_ptr() if v.numel() else None, n_rows, X.data_ptr(), X.stride(0) if X.shape[0] > 1 else d,
               out.data_ptr(), out.stride(0) if n_rows > 1 else d, d, _lib.stream(dev))
+    return out
+
+
+def _panel(t: torch.Tensor, name: str, dev) -> tuple[torch.Tensor, int]:
+    """A 2-D fp32 panel on `dev` with unit column stride and a row stride >= its width (a column window
+    of a wider panel passes as it is; anything else -- expanded, transposed -- is copied), and that
+    row stride in elements."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"sddmm computes in fp32, {name} is {t.dtype}")
+    if t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, the pattern on {dev}")
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be 2-D, got {tuple(t.shape)}")
+    d = t.shape[1]
+    if (d > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < d):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 and t.stride(0) >= d else d)
+
+
+def sddmm(ip, ix, G: torch.Tensor, X: torch.Tensor, perm: torch.Tensor | None = None,
+          out: torch.Tensor | None = None, check: bool = True) -> torch.Tensor:
+    """The sampled dense-dense product (srg_sddmm_f32), spmm's gradient with respect to its values: for
+    every entry e = (r, c) of the device CSR pattern (ip, ix),
+      out[e] = ((((+0 + G[r,0] X[c,0]) + G[r,1] X[c,1]) + ...) + G[r,d-1] X[c,d-1]),
+    columns ascending, every product rounded before it is added; d == 0 gives +0.  G: [rows of the
+    pattern, d], X: [rows the column ids index, d], fp32.  With perm (int64 [nnz], a permutation) entry
+    e's result goes to out[perm[e]].  A panel whose column stride is not 1 is made contiguous; a
+    row-strided column window is passed through with its stride.  check=False skips the checks that
+    read the pattern back (for a pattern this module built itself)."""
+    dev = _dev(ip)
+    n_rows, nnz = ip.numel() - 1, ix.numel()
+    if ix.dtype != torch.int32:
+        raise TypeError("column ids must be int32")
+    G, ldg = _panel(G, "G", dev)
+    X, ldx = _panel(X, "X", dev)
+    if check:
+        _check_csr(ip, ix, ix)                              # a pattern: no values
+        if nnz and (int(ix.min()) < 0 or int(ix.max()) >= X.shape[0]):
+            raise ValueError("column ids must index X's rows")
+    if G.shape[0] != n_rows:
+        raise ValueError(f"the pattern has {n_rows} rows, G {G.shape[0]}")
+    if G.shape[1] != X.shape[1]:
+        raise ValueError(f"G has {G.shape[1]} columns, X {X.shape[1]}")
+    d = G.shape[1]
+    if perm is not None:
+        if perm.dtype != torch.int64 or perm.device != dev or perm.dim() != 1 or perm.numel() != nnz:
+            raise ValueError(f"perm must be an int64 [{nnz}] tensor on {dev}")
+        perm = perm.contiguous()
+    if out is None:
+        out = torch.empty(nnz, dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.device != dev or out.dim() != 1 or out.numel() != nnz
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 [{nnz}] tensor on {dev}")
+    ip, ix = ip.contiguous(), ix.contiguous()
+
+    def ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+    _lib.call(dev, "srg_sddmm_f32", ip.data_ptr(), ptr(ix), n_rows, nnz, ptr(G), ldg, ptr(X), ldx, d, ptr(perm),
+              ptr(out), _lib.stream(dev))
     return out

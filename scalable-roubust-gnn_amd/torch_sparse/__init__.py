@@ -27,8 +27,14 @@ reference pins no version; these are the published torch_sparse 0.6.x semantics,
       -> srgnn.sparse.spgemm_grad (srg_spgemm_grad_f32).
   spmm(index, value, m, n, matrix) -> [m, ...] dense
       index_select, mul, scatter_add: each output row is the sum of its entries' rounded products in
-      index order from 0 -> srgnn.sparse.spmm_scatter (srg_spmm_muladd_f32); differentiable in
-      `matrix` and `value` (the adjoint scatter runs through the same kernel).
+      index order from 0 -> srgnn.sparse.spmm_scatter (srg_spmm_muladd_f32); differentiable (once) in
+      `matrix` (the adjoint scatter runs through the same kernel) and in `value`:
+        g_value[(r,c)] = ((0 + G[r,0] matrix[c,0]) + G[r,1] matrix[c,1]) + ...   columns ascending,
+      products rounded before they are added, every duplicate entry getting the full value, in the
+      caller's entry order -> srgnn.sparse.sddmm (srg_sddmm_f32).  torch_sparse's own value gradient
+      is torch's vectorised sum, whose order depends on the host's SIMD width; this chain is pinned
+      by its host restatement and lies within d * 2^-24 / (1 - d * 2^-24) * sum |G[r,j] matrix[c,j]|
+      of the exact dot product.  Only the sides that require grad are computed.
   coalesce(index, value, m, n, op="add") -> (index, value)
       sorted by row * n + col, each run of equal keys summed in order (srgnn.directed).
 
@@ -125,25 +131,30 @@ def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False):
 
 
 class _SpMM(torch.autograd.Function):
+    """spmm with the value gradient of srgnn.sparse.sddmm, in the caller's entry order."""
+
     @staticmethod
     def forward(ctx, row, col, value, m, matrix):
         from srgnn.sparse import csr_from_coo, spmm_scatter
-        ip, ix, v = csr_from_coo(row, col, value.detach(), m)
-        ctx.save_for_backward(row, col, value, matrix)
+        ip, ix, v, perm = csr_from_coo(row, col, value.detach(), m, return_perm=True)
+        ctx.save_for_backward(row, col, value, matrix, ip, ix, perm)
         ctx.m = m
         return spmm_scatter(ip, ix, v, matrix.detach())
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad):
-        from srgnn.sparse import csr_from_coo, spmm_scatter
-        row, col, value, matrix = ctx.saved_tensors
+        from srgnn.sparse import csr_from_coo, sddmm, spmm_scatter
+        row, col, value, matrix, ip, ix, perm = ctx.saved_tensors
         g_val = g_mat = None
         if ctx.needs_input_grad[4]:
             # adjoint of the scatter: grad_matrix[c] = sum over entries with column c of v * grad[r]
-            ip, ix, v = csr_from_coo(col, row, value.detach(), matrix.shape[0])
-            g_mat = spmm_scatter(ip, ix, v, grad.contiguous())
+            ip_t, ix_t, v = csr_from_coo(col, row, value.detach(), matrix.shape[0])
+            g_mat = spmm_scatter(ip_t, ix_t, v, grad.contiguous())
         if ctx.needs_input_grad[2]:
-            g_val = (grad[row] * matrix[col]).sum(dim=-1)
+            # g_val[(r,c)] = the chain over the columns of grad[r, j] * matrix[c, j]; CSR entry e is the
+            # caller's entry perm[e] (the forward checked the pattern)
+            g_val = sddmm(ip, ix, grad, matrix, perm=perm, check=False)
         return None, None, g_val, None, g_mat
 
 
