@@ -421,6 +421,63 @@ int srg_hop_simweight_f32(const float* x0, int64_t ldx0, const float* y, int64_t
 /* acc[r, :] = acc[r, :] / z[r] (correctly rounded), acc [n_rows, d] with leading dimension lda. */
 int srg_row_divide_f32(float* acc, int64_t lda, const float* z, int64_t n_rows, int32_t d, void* stream);
 
+/* GAMLP's learnable hop attention (SSRG/operators/message_operator/learnable_weighted_messahe_op.py,
+ * combination types gate / ori_ref / jk; the model of models/gamlp.py), forward and backward, without the
+ * [H*n, (T+1)*d] panel the reference's torch composition builds.  Common arguments:
+ * panels / ldp are HOST arrays of T device pointers [n, d] and their leading dimensions (elements, >= d;
+ * column windows of wider panels pass as they are), 1 <= T <= SRG_HOP_MAX; the slice is the H = end - start
+ * panels start .. end-1 (0 <= start < end <= T); w is the weight row of Linear(in_dim, 1), b its bias
+ * (device), in_dim = R + d with R = 0 (gate), d (ori_ref: [hop 0 | hop]) or T*d (jk: [all hops | hop]).
+ * All four are asynchronous on `stream`, deterministic (no atomics; a result's bits depend on the shapes,
+ * the slice and the panels' alignment -- 16-, 8- or 4-byte accesses -- never on the device or the launch)
+ * and within the bound of DESIGN.md §5.4.2 of the formula evaluated exactly; not bit-identical to torch's
+ * CPU result, whose reductions depend on the host.  n == 0 is a no-op. */
+#define SRG_HOP_MAX 32
+#define SRG_HOP_GATE 0
+#define SRG_HOP_ORI_REF 1
+#define SRG_HOP_JK 2
+#define SRG_HOP_PAIR_TRANSPOSE 0   /* gate:        S[i, h] = zflat[h*n + i] */
+#define SRG_HOP_PAIR_FLAT 1        /* ori_ref, jk: S[i, h] = zflat[i*H + h], the reference's .view(-1, H) */
+/* Scores, hop-major: zflat[h*n + i] = (ref(i) + hop(h, i)) + b  (gate: hop(h, i) + b), with
+ *   ref(i)    = sum of w[t*d + c] * F_t[i, c] over the reference panels (jk: t = 0 .. T-1; ori_ref: t = 0)
+ *   hop(h, i) = sum of w[R + c] * F_{start+h}[i, c].
+ * S lanes per row (the power of two >= the row's 16-, 8- or 4-byte chunks, at most 64), lane l takes
+ * chunks l, l + S, ... and folds their elements with fmas in that order: the reference part as one chain
+ * per lane that runs on through the panels t ascending, each hop part as its own chain from +0; the S
+ * partials of a part are added in an xor butterfly (distances S/2, S/4, .., 1); then the two adds above,
+ * correctly rounded.  One pass: a panel row is loaded once for both of its parts. */
+int srg_hop_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                       int kind, const float* w, const float* b, float* zflat, int64_t n, int32_t d, void* stream);
+/* Attend: a = 1 / (1 + expf(-S[i, h])), e = expf(a), P[i, h] = e_h / (e_0 + e_1 + .. + e_{H-1}) (the sum
+ * left to right; adds and divides correctly rounded; a is in (0, 1), so no row maximum is subtracted),
+ * out[i, :] = P[i,0]*F_start[i, :] + P[i,1]*F_{start+1}[i, :] + ... left to right with separate multiply
+ * and add.  P: [n, H] contiguous, kept for the backward; out: [n, d], leading dimension ldo, no alias of a
+ * slice panel.  H = 1 gives P = 1 and out = the panel's bits. */
+int srg_hop_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                       const float* zflat, int pairing, float* P, float* out, int64_t ldo, int64_t n, int32_t d,
+                       void* stream);
+/* Attend gradient for G = dL/dout [n, d] (leading dimension ldg): dP[i, h] = G[i, :] . F_{start+h}[i, :]
+ * (the scores' lane layout: one fma chain per lane from +0, the butterfly), then per row
+ *   t = P_0*dP_0 + P_1*dP_1 + ... (left to right)     da_h = P_h * (dP_h - t)
+ *   dS_h = da_h * (a_h * (1 - a_h))                    a_h recomputed from zflat as in the forward
+ * stored through the inverse pairing: dzflat[q] = dS[i, h] where S[i, h] = zflat[q].  dP: work [n, H];
+ * dzflat: [H*n]; neither aliases zflat or P. */
+int srg_hop_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                            const float* G, int64_t ldg, const float* zflat, const float* P, int pairing,
+                            float* dP, float* dzflat, int64_t n, int32_t d, void* stream);
+/* Parameter gradient: dw [in_dim] and db [1] (either may be NULL: not computed) from dzflat, in two stages.
+ * s[i] = dz[0,i] + dz[1,i] + ... (left to right).  Stage 1: group q owns rows [q*rpg, (q+1)*rpg), rpg = the
+ * smallest 32 * 2^k with rpg * 2048 >= n -- a function of n alone, never of the device; per group, panel
+ * and column one fma chain from +0 over the rows ascending,
+ *   ref part t: fma(s[i], F_t[i, c], .)        hop part h: fma(dz[h, i], F_{start+h}[i, c], .)
+ * the group's hop parts added in ascending h, its bias part s[i0] + s[i0+1] + ...  Stage 2 adds the
+ * groups' partials in group order.  `scratch`: device, 16-byte aligned, srg_hop_scores_grad_scratch_bytes()
+ * bytes (s and the partials).  n == 0 stores zeros. */
+int srg_hop_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t T, int32_t H, int kind, int64_t* bytes);
+int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                            int kind, const float* dzflat, float* dw, float* db, void* scratch, int64_t n,
+                            int32_t d, void* stream);
+
 /* srg_spmm_csr_f32 with the aggregation step fused into its epilogue: Y = A*X as above and, for
  * every element y stored, agg = (agg_init ? 0 : agg) + w*y (separate multiply / add) -- the same
  * result as srg_spmm_csr_f32 followed by srg_hop_accumulate_f32(INIT or ADD), one panel pass less.

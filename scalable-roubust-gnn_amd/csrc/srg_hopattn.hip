@@ -1,0 +1,506 @@
+// srg_hopattn.hip -- the learnable hop attention of GAMLP (SSRG/operators/message_operator/
+// learnable_weighted_messahe_op.py, combination types gate / ori_ref / jk), forward and backward, without
+// the [H*n, (T+1)*d] panel the reference's torch composition builds: scores, attend, attend gradient and
+// the parameter gradient, each a streaming pass over the hop panels.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "srgnn_hip.h"
+#include "srg_internal.h"
+#include "srg_device.h"
+
+namespace {
+
+// The hop list as a kernel argument: T device pointers and their row strides (elements).  Indexed with
+// wave-uniform t only.
+struct HopPanels {
+    const float* p[SRG_HOP_MAX];
+    int64_t ld[SRG_HOP_MAX];
+};
+
+// what panel t contributes to: the reference part of the score (jk: every panel; ori_ref: panel 0) and /
+// or the hop part of the slice position t - start
+__device__ __forceinline__ bool is_ref(int kind, int t) { return kind == SRG_HOP_JK || (kind == SRG_HOP_ORI_REF && t == 0); }
+__host__ __device__ __forceinline__ int64_t pad4(int64_t x) { return (x + 3) / 4 * 4; }
+__host__ __device__ __forceinline__ int ref_dim(int kind, int T, int d)
+{
+    return kind == SRG_HOP_JK ? T * d : kind == SRG_HOP_ORI_REF ? d : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// scores: zflat[h * n + i] = (ref(i) + hop(h, i)) + b   (gate: hop(h, i) + b)
+//   ref(i)    = sum over the reference panels t ascending, columns in lane order, of w[t*d + c] * F_t[i, c]
+//   hop(h, i) = sum over the columns of w[R + c] * F_{start+h}[i, c],  R = the reference part's length
+// The lane layout is k_hop_simweight's: S = 2^lgS lanes per row (the power of two >= the row's
+// VEC-chunks, at most 64), 64 / S rows per wave step, lane c0 of a row takes chunks c0, c0 + S, ... and
+// folds them with fmas in that order -- the reference part as ONE chain per lane that runs on through the
+// panels t = 0, 1, ..., each hop part as a chain of its own from +0 -- and the S partials are added in an
+// xor butterfly.  A panel row is loaded once and feeds both parts.  A hop part waits in zflat (written
+// and read back by the same lane) until the last reference panel is folded in.  A row's bits depend on
+// d, T, the slice and VEC only.  (Loading the rows of four panels ahead of the first fold measured slower,
+// 0.49 against 0.30 ms at n = 200,000, T = 11, d = 128: 100 registers per lane instead of 30.)
+// ------------------------------------------------------------------------------------------------
+template <int VEC>
+__global__ void __launch_bounds__(256)
+k_hop_scores(HopPanels pl, int T, int start, int H, int kind, const float* __restrict__ w,
+             const float* __restrict__ b, float* __restrict__ zflat, int64_t n, int d, int cpr, int lgS)
+{
+    typedef typename Vec<float, VEC>::type V;
+    const int S = 1 << lgS, R = 64 >> lgS;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> lgS, c0 = lane & (S - 1);
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const float* wh = w + ref_dim(kind, T, d);
+    const float bias = b[0];
+    // every lane of the wave runs every step (the butterfly reads its partners); rows past the end load nothing
+    for (int64_t base = wave * R; base < n; base += waves * R) {
+        const int64_t r = base + g;
+        const bool live = r < n;
+        float ref = 0.0f;
+        for (int t = 0; t < T; ++t) {
+            const int h = t - start;
+            const bool hop = h >= 0 && h < H, rf = is_ref(kind, t);
+            if (!hop && !rf) continue;
+            const float* xr = pl.p[t] + r * pl.ld[t];
+            const float* wr = w + (int64_t)t * d;
+            float hp = 0.0f;
+            for (int c = c0; live && c < cpr; c += S) {
+                const V xc = vload<float, VEC>(xr + (int64_t)c * VEC);
+                if (rf) {
+                    const V wc = vload<float, VEC>(wr + (int64_t)c * VEC);
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) ref = __builtin_fmaf(elem(wc, j), elem(xc, j), ref);
+                }
+                if (hop) {
+                    const V wc = vload<float, VEC>(wh + (int64_t)c * VEC);
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) hp = __builtin_fmaf(elem(wc, j), elem(xc, j), hp);
+                }
+            }
+            if (hop) {
+                for (int m = S >> 1; m > 0; m >>= 1) hp = __fadd_rn(hp, __shfl_xor(hp, m));
+                if (live && c0 == (h & (S - 1))) zflat[(int64_t)h * n + r] = hp;
+            }
+        }
+        for (int m = S >> 1; m > 0; m >>= 1) ref = __fadd_rn(ref, __shfl_xor(ref, m));
+        for (int h = c0; live && h < H; h += S) {
+            float z = zflat[(int64_t)h * n + r];
+            if (kind != SRG_HOP_GATE) z = __fadd_rn(ref, z);
+            zflat[(int64_t)h * n + r] = __fadd_rn(z, bias);
+        }
+    }
+}
+
+// The score of node i at slice position h: the true transpose (gate) or the reference's .view(-1, H) of
+// the hop-major vector (ori_ref, jk).
+__device__ __forceinline__ int64_t paired(int flat, int64_t i, int h, int64_t n, int H)
+{
+    return flat ? i * H + h : (int64_t)h * n + i;
+}
+
+// P[i, h] = e_h / (e_0 + e_1 + ... + e_{H-1}), e_h = expf(a_h), a_h = 1 / (1 + expf(-S[i, h])): one thread
+// per row, the sum left to right from e_0, every add and divide correctly rounded.  a is in (0, 1), so no
+// maximum is subtracted.
+__global__ void __launch_bounds__(256)
+k_hop_softmax(const float* __restrict__ zflat, int flat, float* __restrict__ P, int64_t n, int H)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        float* pr = P + i * H;
+        float sum = 0.0f;
+        for (int h = 0; h < H; ++h) {
+            const float s = zflat[paired(flat, i, h, n, H)];
+            const float a = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-s)));
+            const float e = expf(a);
+            pr[h] = e;
+            sum = h == 0 ? e : __fadd_rn(sum, e);
+        }
+        for (int h = 0; h < H; ++h) pr[h] = __fdiv_rn(pr[h], sum);
+    }
+}
+
+// out[i, :] = P[i, 0] * F_0[i, :] + P[i, 1] * F_1[i, :] + ... in ascending h, separate multiply and add.
+template <int VEC>
+__global__ void __launch_bounds__(256)
+k_hop_combine(HopPanels pl, int start, int H, const float* __restrict__ P, float* __restrict__ out, int64_t ldo,
+              int64_t n, int cpr, int lgS)
+{
+    typedef typename Vec<float, VEC>::type V;
+    const int S = 1 << lgS, R = 64 >> lgS;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> lgS, c0 = lane & (S - 1);
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t base = wave * R; base < n; base += waves * R) {
+        const int64_t r = base + g;
+        if (r >= n) continue;
+        const float* pr = P + r * H;
+        for (int c = c0; c < cpr; c += S) {
+            V acc;
+#pragma unroll 4
+            for (int h = 0; h < H; ++h) {
+                const V xc = vload<float, VEC>(pl.p[start + h] + r * pl.ld[start + h] + (int64_t)c * VEC);
+                const float ph = pr[h];
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    const float t = __fmul_rn(ph, elem(xc, j));
+                    elem(acc, j) = h == 0 ? t : __fadd_rn(elem(acc, j), t);
+                }
+            }
+            vstore<float, VEC>(out + r * ldo + (int64_t)c * VEC, acc, false);
+        }
+    }
+}
+
+// dP[i, h] = G[i, :] . F_{start+h}[i, :]: the scores' lane layout, one fma chain per lane from +0 in chunk
+// order, xor butterfly.
+template <int VEC>
+__global__ void __launch_bounds__(256)
+k_hop_rowdots(HopPanels pl, int start, int H, const float* __restrict__ G, int64_t ldg, float* __restrict__ dP,
+              int64_t n, int cpr, int lgS)
+{
+    typedef typename Vec<float, VEC>::type V;
+    const int S = 1 << lgS, R = 64 >> lgS;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> lgS, c0 = lane & (S - 1);
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t base = wave * R; base < n; base += waves * R) {
+        const int64_t r = base + g;
+        const bool live = r < n;
+        const float* gr = G + r * ldg;
+        for (int h = 0; h < H; ++h) {
+            const float* xr = pl.p[start + h] + r * pl.ld[start + h];
+            float dot = 0.0f;
+            for (int c = c0; live && c < cpr; c += S) {
+                const V xc = vload<float, VEC>(xr + (int64_t)c * VEC);
+                const V gc = vload<float, VEC>(gr + (int64_t)c * VEC);
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) dot = __builtin_fmaf(elem(gc, j), elem(xc, j), dot);
+            }
+            for (int m = S >> 1; m > 0; m >>= 1) dot = __fadd_rn(dot, __shfl_xor(dot, m));
+            if (live && c0 == (h & (S - 1))) dP[r * H + h] = dot;
+        }
+    }
+}
+
+// The softmax and sigmoid Jacobians of one row, one thread per row:
+//   t = P_0 dP_0 + P_1 dP_1 + ... (left to right)      da_h = P_h * (dP_h - t)
+//   dS_h = da_h * (a_h * (1 - a_h)),  a_h recomputed from the score as in the forward
+// stored where the score came from (the inverse pairing).
+__global__ void __launch_bounds__(256)
+k_hop_jacobian(const float* __restrict__ zflat, int flat, const float* __restrict__ P, const float* __restrict__ dP,
+               float* __restrict__ dzflat, int64_t n, int H)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float* pr = P + i * H;
+        const float* dr = dP + i * H;
+        float t = 0.0f;
+        for (int h = 0; h < H; ++h) {
+            const float m = __fmul_rn(pr[h], dr[h]);
+            t = h == 0 ? m : __fadd_rn(t, m);
+        }
+        for (int h = 0; h < H; ++h) {
+            const int64_t q = paired(flat, i, h, n, H);
+            const float a = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-zflat[q])));
+            const float da = __fmul_rn(pr[h], __fsub_rn(dr[h], t));
+            dzflat[q] = __fmul_rn(da, __fmul_rn(a, __fsub_rn(1.0f, a)));
+        }
+    }
+}
+
+// s[i] = dz[0, i] + dz[1, i] + ... (left to right): the reference part's and the bias's per-node factor
+__global__ void __launch_bounds__(256)
+k_hop_dzsum(const float* __restrict__ dzflat, float* __restrict__ s, int64_t n, int H)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        float t = dzflat[i];
+        for (int h = 1; h < H; ++h) t = __fadd_rn(t, dzflat[(int64_t)h * n + i]);
+        s[i] = t;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// parameter gradient, stage 1.  Group q owns rows [q * rpg, (q + 1) * rpg); CT = 2^lgCT threads of a
+// workgroup serve one group (256 / CT groups per workgroup), thread c0 owning the VEC columns of chunk
+// tile * CT + c0 (blockIdx.y = tile: wide rows take more tiles, not more registers).  Per panel t, rows
+// ascending, one fma per row and column:
+//   ref_t[c] = fma(s[i], F_t[i, c], ref_t[c])              -> partials[q, t*d + c]
+//   hop_h[c] = fma(dz[h, i], F_t[i, c], hop_h[c]), h = t - start
+// a panel row loaded once for both; the hop parts are added in ascending h (the first as it is) into
+// partials[q, R + c]; the group's bias part s[i0] + s[i0+1] + ... goes to partials[q, in_dim].
+// ------------------------------------------------------------------------------------------------
+template <int VEC>
+__global__ void __launch_bounds__(256)
+k_hop_wgrad_partial(HopPanels pl, int T, int start, int H, int kind, const float* __restrict__ dzflat,
+                    const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d, int cpr, int lgCT,
+                    int64_t rpg, int64_t n_groups, int want_w)
+{
+    typedef typename Vec<float, VEC>::type V;
+    const int CT = 1 << lgCT;
+    const int c0 = threadIdx.x & (CT - 1);
+    const int64_t q = (int64_t)blockIdx.x * (256 >> lgCT) + (threadIdx.x >> lgCT);
+    if (q >= n_groups) return;
+    const int c = blockIdx.y * CT + c0;
+    const int rd = ref_dim(kind, T, d);
+    const int64_t ldq = pad4((int64_t)rd + d + 1);
+    float* out = partials + q * ldq;
+    const int64_t i0 = q * rpg, i1 = i0 + rpg < n ? i0 + rpg : n;
+    if (c == 0) {
+        float t = s[i0];
+        for (int64_t i = i0 + 1; i < i1; ++i) t = __fadd_rn(t, s[i]);
+        out[rd + d] = t;
+    }
+    if (!want_w || c >= cpr) return;
+    V tot;
+    for (int t = 0; t < T; ++t) {
+        const int h = t - start;
+        const bool hop = h >= 0 && h < H, rf = is_ref(kind, t);
+        if (!hop && !rf) continue;
+        const float* x = pl.p[t] + (int64_t)c * VEC;
+        const int64_t ldx = pl.ld[t];
+        const float* dz = dzflat + (int64_t)(hop ? h : 0) * n;
+        V ra = vzero<float, VEC>(), ha = vzero<float, VEC>();
+#pragma unroll 4
+        for (int64_t i = i0; i < i1; ++i) {
+            const V xc = vload<float, VEC>(x + i * ldx);
+            const float si = s[i], di = dz[i];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                if (rf) elem(ra, j) = __builtin_fmaf(si, elem(xc, j), elem(ra, j));
+                if (hop) elem(ha, j) = __builtin_fmaf(di, elem(xc, j), elem(ha, j));
+            }
+        }
+        if (rf) vstore<float, VEC>(out + (int64_t)t * d + (int64_t)c * VEC, ra, false);
+        if (hop) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) elem(tot, j) = h == 0 ? elem(ha, j) : __fadd_rn(elem(tot, j), elem(ha, j));
+        }
+    }
+    vstore<float, VEC>(out + rd + (int64_t)c * VEC, tot, false);
+}
+
+// stage 2: column j of the partials folded in group order, the first as it is
+__global__ void __launch_bounds__(256)
+k_hop_wgrad_fold(const float* __restrict__ partials, int64_t n_groups, int in_dim, float* __restrict__ dw,
+                 float* __restrict__ db)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > in_dim) return;
+    const int64_t ldq = pad4((int64_t)in_dim + 1);
+    if (j < in_dim ? dw == nullptr : db == nullptr) return;
+    float t = partials[j];
+#pragma unroll 32
+    for (int64_t q = 1; q < n_groups; ++q) t = __fadd_rn(t, partials[q * ldq + j]);
+    if (j < in_dim) dw[j] = t; else db[0] = t;
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct HopShape {
+    HopPanels pl;
+    int vec, cpr, lgS;
+    unsigned row_blocks;      // the row-streaming kernels' grid (grid-stride over the row steps)
+    unsigned thread_blocks;   // the one-thread-per-row kernels' grid
+};
+
+// rows per group of the parameter gradient's stage 1: a function of n alone (srgnn_hip.h)
+int64_t rows_per_group(int64_t n)
+{
+    int64_t rpg = 32;
+    while (rpg * 2048 < n) rpg *= 2;
+    return rpg;
+}
+
+// Checks the hop list and the slice, and picks the access width every row of every panel and of the
+// `wide` operands (read or written in chunks: pointer and row stride, 0 for a vector) is aligned for.
+int hop_shape(const float* const* panels, const int64_t* ldp, int T, int start, int end, int64_t n, int d,
+              const void* const* wide, const int64_t* wide_ld, int n_wide, HopShape& hs)
+{
+    if (T < 1 || T > SRG_HOP_MAX) return srg_fail(SRG_ERR_INVALID, "T=%d hop panels: 1 .. %d", T, SRG_HOP_MAX);
+    if (start < 0 || end <= start || end > T)
+        return srg_fail(SRG_ERR_INVALID, "hop slice [%d, %d) of %d panels", start, end, T);
+    if (n < 0 || d < 1) return srg_fail(SRG_ERR_INVALID, "bad shape n=%lld d=%d", (long long)n, d);
+    if ((int64_t)T * d + d + 1 > INT32_MAX) return srg_fail(SRG_ERR_INVALID, "T*d = %d*%d too wide", T, d);
+    if (n == 0) return SRG_OK;
+    if (!panels || !ldp) return srg_fail(SRG_ERR_INVALID, "null panel list");
+    for (int t = 0; t < T; ++t) {
+        if (!panels[t] || ldp[t] < d)
+            return srg_fail(SRG_ERR_INVALID, "panel %d: pointer %p, leading dimension %lld < d=%d", t,
+                            (const void*)panels[t], (long long)ldp[t], d);
+        hs.pl.p[t] = panels[t];
+        hs.pl.ld[t] = ldp[t];
+    }
+    for (int t = T; t < SRG_HOP_MAX; ++t) { hs.pl.p[t] = nullptr; hs.pl.ld[t] = 0; }
+    for (int e = 0; e < n_wide; ++e)
+        if (!wide[e]) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    hs.vec = 1;
+    for (int v = 4; v > 1 && hs.vec == 1; v >>= 1) {
+        const size_t a = v * sizeof(float);
+        bool ok = d % v == 0;
+        for (int t = 0; ok && t < T; ++t) ok = ldp[t] % v == 0 && aligned(panels[t], a);
+        for (int e = 0; ok && e < n_wide; ++e) ok = wide_ld[e] % v == 0 && aligned(wide[e], a);
+        if (ok) hs.vec = v;
+    }
+    hs.cpr = d / hs.vec;
+    hs.lgS = 0;
+    while (hs.lgS < 6 && (1 << hs.lgS) < hs.cpr) ++hs.lgS;
+    const int64_t rows_per_block = (int64_t)(256 / 64) * (64 >> hs.lgS);
+    hs.row_blocks = (unsigned)std::min<int64_t>((n + rows_per_block - 1) / rows_per_block, 256 * 64);
+    hs.thread_blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 256 * 16);
+    return SRG_OK;
+}
+
+int check_kind(int kind)
+{
+    if (kind != SRG_HOP_GATE && kind != SRG_HOP_ORI_REF && kind != SRG_HOP_JK)
+        return srg_fail(SRG_ERR_INVALID, "hop attention kind %d", kind);
+    return SRG_OK;
+}
+
+int check_pairing(int pairing)
+{
+    if (pairing != SRG_HOP_PAIR_TRANSPOSE && pairing != SRG_HOP_PAIR_FLAT)
+        return srg_fail(SRG_ERR_INVALID, "hop attention pairing %d", pairing);
+    return SRG_OK;
+}
+
+#define SRG_HOP_BY_VEC(vec, LAUNCH)   \
+    do {                              \
+        if ((vec) == 4) { LAUNCH(4); } else if ((vec) == 2) { LAUNCH(2); } else { LAUNCH(1); } \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int srg_hop_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                       int kind, const float* w, const float* b, float* zflat, int64_t n, int32_t d, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    if (int rc = check_kind(kind)) return rc;
+    HopShape hs;
+    const void* wide[] = {w};
+    const int64_t wide_ld[] = {0};
+    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, wide, wide_ld, 1, hs)) return rc;
+    if (n == 0) return srg_ok();
+    if (!b || !zflat) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    const int H = end - start;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_scores<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, T, start, H, kind, \
+                                     w, b, zflat, n, d, hs.cpr, hs.lgS)
+    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#undef LAUNCH
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_hop_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                       const float* zflat, int pairing, float* P, float* out, int64_t ldo, int64_t n, int32_t d,
+                       void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    if (int rc = check_pairing(pairing)) return rc;
+    HopShape hs;
+    const void* wide[] = {out};
+    const int64_t wide_ld[] = {ldo};
+    if (ldo < d) return srg_fail(SRG_ERR_INVALID, "ldo=%lld < d=%d", (long long)ldo, d);
+    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, wide, wide_ld, 1, hs)) return rc;
+    if (n == 0) return srg_ok();
+    if (!zflat || !P) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    const int H = end - start;
+    for (int t = start; t < end; ++t)
+        if (out == panels[t]) return srg_fail(SRG_ERR_INVALID, "out must not alias a hop panel");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_hop_softmax, dim3(hs.thread_blocks), dim3(256), 0, st, zflat, pairing, P, n, H);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_combine<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, P, out, \
+                                     ldo, n, hs.cpr, hs.lgS)
+    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#undef LAUNCH
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_hop_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                            const float* G, int64_t ldg, const float* zflat, const float* P, int pairing,
+                            float* dP, float* dzflat, int64_t n, int32_t d, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    if (int rc = check_pairing(pairing)) return rc;
+    HopShape hs;
+    const void* wide[] = {G};
+    const int64_t wide_ld[] = {ldg};
+    if (ldg < d) return srg_fail(SRG_ERR_INVALID, "ldg=%lld < d=%d", (long long)ldg, d);
+    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, wide, wide_ld, 1, hs)) return rc;
+    if (n == 0) return srg_ok();
+    if (!zflat || !P || !dP || !dzflat) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    if (dzflat == zflat || dP == P) return srg_fail(SRG_ERR_INVALID, "dzflat / dP must not alias zflat / P");
+    const int H = end - start;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_rowdots<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, G, ldg, \
+                                     dP, n, hs.cpr, hs.lgS)
+    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#undef LAUNCH
+    hipLaunchKernelGGL(k_hop_jacobian, dim3(hs.thread_blocks), dim3(256), 0, st, zflat, pairing, P, dP, dzflat, n, H);
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_hop_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t T, int32_t H, int kind, int64_t* bytes)
+{
+    if (int rc = check_kind(kind)) return rc;
+    if (!bytes) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    if (n < 0 || d < 1 || T < 1 || T > SRG_HOP_MAX || H < 1 || H > T)
+        return srg_fail(SRG_ERR_INVALID, "bad shape n=%lld d=%d T=%d H=%d", (long long)n, d, T, H);
+    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
+    // s [n], then partials [n_groups, in_dim + 1], each row of either rounded up to 16 bytes
+    *bytes = (pad4(n) + n_groups * pad4((int64_t)ref_dim(kind, T, d) + d + 1)) * (int64_t)sizeof(float);
+    return srg_ok();
+}
+
+int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                            int kind, const float* dzflat, float* dw, float* db, void* scratch, int64_t n,
+                            int32_t d, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    if (int rc = check_kind(kind)) return rc;
+    HopShape hs;
+    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, nullptr, nullptr, 0, hs)) return rc;
+    if (!dw && !db) return srg_ok();
+    const int H = end - start;
+    const int rd = ref_dim(kind, T, d), in_dim = rd + d;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {   // empty sums
+        if (dw) SRG_HIP_CHECK(hipMemsetAsync(dw, 0, (size_t)in_dim * sizeof(float), st));
+        if (db) SRG_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float), st));
+        return srg_ok();
+    }
+    if (!dzflat || !scratch || !aligned(scratch, 16))
+        return srg_fail(SRG_ERR_INVALID, "dzflat or scratch null, or scratch not 16-byte aligned");
+    const int vec = hs.vec, cpr = hs.cpr;
+    int lgCT = 0;
+    while (lgCT < 8 && (1 << lgCT) < cpr) ++lgCT;
+    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
+    float* s = static_cast<float*>(scratch);
+    float* partials = s + pad4(n);
+    const int groups_per_block = 256 >> lgCT;
+    const dim3 grid((unsigned)((n_groups + groups_per_block - 1) / groups_per_block),
+                    (unsigned)((cpr + (1 << lgCT) - 1) >> lgCT));
+    hipLaunchKernelGGL(k_hop_dzsum, dim3(hs.thread_blocks), dim3(256), 0, st, dzflat, s, n, H);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_wgrad_partial<V>), grid, dim3(256), 0, st, hs.pl, T, start, H, kind, dzflat, \
+                                     s, partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr)
+    SRG_HOP_BY_VEC(vec, LAUNCH);
+#undef LAUNCH
+    hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials,
+                       n_groups, in_dim, dw, db);
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+}  // extern "C"

@@ -7,6 +7,11 @@ the same initial values), same forward arithmetic.
     gate                       (feat_dim)             per-node weights from Linear(feat_dim, 1) on each hop
     ori_ref                    (feat_dim)             ... on [hop 0 | hop]
     jk                         (prop_steps, feat_dim) ... on [all hops | hop]
+
+`fused` (default False): with it set, gate / ori_ref / jk over hop tensors held on a HIP device, none of
+which requires grad, run srgnn.hop_attention (the device kernels of DESIGN.md §5.4.2: the same weights
+within a derived rounding bound, gradients for the Linear's weight and bias, none of the composition's
+[hops * n, in_dim] temporaries).  Everything else takes the composition below, unchanged.
 """
 import torch
 import torch.nn.functional as F
@@ -40,6 +45,7 @@ class LearnableWeightedMessageOp(MessageOp):
             if combination_type == "jk":
                 in_dim = args[1] + (args[0] + 1) * args[1]
             self.learnable_weight = nn.Linear(in_dim, 1)
+        self.fused = False
 
     def _hop_weights(self, feat_list):
         hops = self.end - self.start
@@ -58,6 +64,11 @@ class LearnableWeightedMessageOp(MessageOp):
 
     def combine(self, feat_list):
         feat_list = squeeze_first_dimension(feat_list)
+        if (self.fused and self.combination_type in ("gate", "ori_ref", "jk") and isinstance(feat_list, list)
+                and all(isinstance(f, torch.Tensor) and f.is_cuda and not f.requires_grad for f in feat_list)):
+            from srgnn.hop_attention import hop_attention
+            return hop_attention(feat_list, self.start, self.end, self.combination_type,
+                                 self.learnable_weight.weight, self.learnable_weight.bias)
         weights = self._hop_weights(feat_list)
         add = one_dim_weighted_add if self.combination_type in ("simple", "simple_allow_neg") else two_dim_weighted_add
         return add(feat_list[self.start:self.end], weight_list=weights)

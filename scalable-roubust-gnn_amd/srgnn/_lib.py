@@ -45,6 +45,12 @@ SRG_ACC_MAX = 5
 SRG_SIM_INIT = 0x1
 SRG_SIM_HOP0 = 0x2
 SRG_TAIL_MAX = 32
+SRG_HOP_MAX = 32
+SRG_HOP_GATE = 0
+SRG_HOP_ORI_REF = 1
+SRG_HOP_JK = 2
+SRG_HOP_PAIR_TRANSPOSE = 0
+SRG_HOP_PAIR_FLAT = 1
 
 SRG_SPGEMM_SERIAL_B = 0x1
 
@@ -97,6 +103,11 @@ EXPORTED_SYMBOLS = (
     "srg_hop_accumulate_f32",
     "srg_hop_simweight_f32",
     "srg_row_divide_f32",
+    "srg_hop_scores_f32",
+    "srg_hop_attend_f32",
+    "srg_hop_attend_grad_f32",
+    "srg_hop_scores_grad_scratch_bytes",
+    "srg_hop_scores_grad_f32",
     "srg_spmm_agg_f32",
     "srg_spmm_span_f32",
     "srg_spmm_cheby_f32",
@@ -209,6 +220,15 @@ def _declare(lib):
     lib.srg_hop_simweight_f32.restype = ctypes.c_int
     lib.srg_row_divide_f32.argtypes = [_p, _i64, _p, _i64, _i32, _p]
     lib.srg_row_divide_f32.restype = ctypes.c_int
+    lib.srg_hop_scores_f32.argtypes = [_p, _p, _i32, _i32, _i32, ctypes.c_int, _p, _p, _p, _i64, _i32, _p]
+    lib.srg_hop_attend_f32.argtypes = [_p, _p, _i32, _i32, _i32, _p, ctypes.c_int, _p, _p, _i64, _i64, _i32, _p]
+    lib.srg_hop_attend_grad_f32.argtypes = [_p, _p, _i32, _i32, _i32, _p, _i64, _p, _p, ctypes.c_int, _p, _p, _i64,
+                                            _i32, _p]
+    lib.srg_hop_scores_grad_scratch_bytes.argtypes = [_i64, _i32, _i32, _i32, ctypes.c_int, ctypes.POINTER(_i64)]
+    lib.srg_hop_scores_grad_f32.argtypes = [_p, _p, _i32, _i32, _i32, ctypes.c_int, _p, _p, _p, _p, _i64, _i32, _p]
+    for name in ("srg_hop_scores_f32", "srg_hop_attend_f32", "srg_hop_attend_grad_f32",
+                 "srg_hop_scores_grad_scratch_bytes", "srg_hop_scores_grad_f32"):
+        getattr(lib, name).restype = ctypes.c_int
     lib.srg_tail_record_f32.argtypes = [_p, _p, _i64, _i32, _i64, _i32, _f32, _p]
     lib.srg_tail_record_f32.restype = ctypes.c_int
     lib.srg_tail_rowsum_f32.argtypes = [_p, _i64, _i32, _i64, _i32, _p, _i32, _p]

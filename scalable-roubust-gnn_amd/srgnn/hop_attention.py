@@ -1,0 +1,138 @@
+"""GAMLP's learnable hop attention on the device (LearnableWeightedMessageOp, combination types gate /
+ori_ref / jk): srg_hop_scores_f32 + srg_hop_attend_f32 forward, srg_hop_attend_grad_f32 +
+srg_hop_scores_grad_f32 backward, without the [H*n, (T+1)*d] panel of the torch composition
+(DESIGN.md §5.4.2).  The hop panels are precomputed constants: gradients go to the weight and the bias.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from srgnn import _lib
+
+KINDS = {"gate": _lib.SRG_HOP_GATE, "ori_ref": _lib.SRG_HOP_ORI_REF, "jk": _lib.SRG_HOP_JK}
+
+
+def in_dim(kind: str, T: int, d: int) -> int:
+    """Input width of the operator's Linear for a list of T hops of d columns."""
+    return {"gate": d, "ori_ref": 2 * d, "jk": T * d + d}[kind]
+
+
+def _pairing(kind: str) -> int:
+    # the reference transposes gate's scores and .view(-1, H)s the hop-major vector of the other two
+    return _lib.SRG_HOP_PAIR_TRANSPOSE if kind == "gate" else _lib.SRG_HOP_PAIR_FLAT
+
+
+def _panel_args(feats):
+    T = len(feats)
+    ptrs = (ctypes.c_void_p * T)(*[f.data_ptr() for f in feats])
+    lds = (ctypes.c_int64 * T)(*[f.stride(0) if f.shape[0] > 1 else f.shape[1] for f in feats])
+    return ptrs, lds
+
+
+def _check(feat_list, start, end, kind, weight, bias):
+    if kind not in KINDS:
+        raise ValueError(f"hop_attention: kind {kind!r} is not one of {sorted(KINDS)}")
+    if not isinstance(feat_list, (list, tuple)) or len(feat_list) == 0:
+        raise ValueError("hop_attention: feat_list must be a non-empty list of hop tensors")
+    T = len(feat_list)
+    if T > _lib.SRG_HOP_MAX:
+        raise ValueError(f"hop_attention: {T} hop tensors, at most {_lib.SRG_HOP_MAX}")
+    start, end = 0 if start is None else int(start), T if end is None else int(end)
+    H = end - start
+    if start < 0 or H < 1 or end > T:
+        # the reference sizes its score matrix by end - start: a slice the list cannot fill is an error there too
+        raise ValueError(f"hop_attention: hop slice [{start}, {end}) of {T} hops")
+    if H > _lib.SRG_HOP_MAX:
+        raise ValueError(f"hop_attention: {H} hops in the slice, at most {_lib.SRG_HOP_MAX}")
+    f0 = feat_list[0]
+    for k, f in enumerate(feat_list):
+        if not isinstance(f, torch.Tensor) or f.dim() != 2:
+            raise ValueError(f"hop_attention: hop {k} is not a 2-d tensor")
+        if f.requires_grad:
+            raise ValueError(f"hop_attention: hop {k} requires grad; the fused path treats the hops as constants")
+        if f.dtype != torch.float32:
+            raise TypeError(f"hop_attention: hop {k} is {f.dtype}, the fused path computes in float32")
+        if not f.is_cuda:
+            raise ValueError(f"hop_attention: hop {k} is on {f.device}, not on a HIP device")
+        if f.shape != f0.shape or f.device != f0.device:
+            raise ValueError(f"hop_attention: hop {k} is {tuple(f.shape)} on {f.device}, hop 0 "
+                             f"{tuple(f0.shape)} on {f0.device}")
+        if f.shape[1] < 1 or f.stride(1) != 1:
+            raise ValueError(f"hop_attention: hop {k} needs >= 1 column and unit column stride")
+    want = in_dim(kind, T, f0.shape[1])
+    if weight.numel() != want or bias.numel() != 1:
+        raise ValueError(f"hop_attention: {kind} over {T} hops of {f0.shape[1]} columns needs a weight of "
+                         f"{want} elements and one bias, got {weight.numel()} and {bias.numel()}")
+    for name, p in (("weight", weight), ("bias", bias)):
+        if p.dtype != torch.float32 or p.device != f0.device:
+            raise TypeError(f"hop_attention: {name} is {p.dtype} on {p.device}, the hops float32 on {f0.device}")
+    return start, end
+
+
+class _HopAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, bias, start, end, kind, *feats):
+        dev = feats[0].device
+        n, d = feats[0].shape
+        T, H = len(feats), end - start
+        w = weight.detach().contiguous().view(-1)
+        b = bias.detach().contiguous().view(-1)
+        ptrs, lds = _panel_args(feats)
+        zflat = torch.empty(H * n, dtype=torch.float32, device=dev)
+        P = torch.empty((n, H), dtype=torch.float32, device=dev)
+        out = torch.empty((n, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.stream(dev)
+            _lib.call(dev, "srg_hop_scores_f32", ptrs, lds, T, start, end, KINDS[kind], w.data_ptr(), b.data_ptr(),
+                      zflat.data_ptr(), n, d, st)
+            _lib.call(dev, "srg_hop_attend_f32", ptrs, lds, T, start, end, zflat.data_ptr(), _pairing(kind),
+                      P.data_ptr(), out.data_ptr(), d, n, d, st)
+        ctx.save_for_backward(P, zflat, *feats)
+        ctx.meta = (start, end, kind, weight.shape, bias.shape)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        P, zflat, *feats = ctx.saved_tensors
+        start, end, kind, w_shape, b_shape = ctx.meta
+        want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none = (None,) * (3 + len(feats))
+        if not (want_w or want_b):
+            return (None, None) + none
+        dev = feats[0].device
+        n, d = feats[0].shape
+        T, H = len(feats), end - start
+        G = grad if grad.dtype == torch.float32 and grad.stride(1) == 1 and (n <= 1 or grad.stride(0) >= d) \
+            else grad.to(torch.float32).contiguous()
+        ldg = G.stride(0) if n > 1 else d
+        ptrs, lds = _panel_args(feats)
+        dP = torch.empty((n, H), dtype=torch.float32, device=dev)
+        dz = torch.empty(H * n, dtype=torch.float32, device=dev)
+        dw = torch.empty(in_dim(kind, T, d), dtype=torch.float32, device=dev) if want_w else None
+        db = torch.empty(1, dtype=torch.float32, device=dev) if want_b else None
+        nbytes = ctypes.c_int64(0)
+        _lib.check(_lib.query("srg_hop_scores_grad_scratch_bytes", n, d, T, H, KINDS[kind], ctypes.byref(nbytes)),
+                   "srg_hop_scores_grad_scratch_bytes")
+        with torch.cuda.device(dev):
+            st = _lib.stream(dev)
+            _lib.call(dev, "srg_hop_attend_grad_f32", ptrs, lds, T, start, end, G.data_ptr(), ldg, zflat.data_ptr(),
+                      P.data_ptr(), _pairing(kind), dP.data_ptr(), dz.data_ptr(), n, d, st)
+            del dP
+            scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+            _lib.call(dev, "srg_hop_scores_grad_f32", ptrs, lds, T, start, end, KINDS[kind], dz.data_ptr(),
+                      dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
+                      n, d, st)
+        return (dw.view(w_shape) if want_w else None, db.view(b_shape) if want_b else None) + none
+
+
+def hop_attention(feat_list, start, end, kind, weight, bias):
+    """out[i] = sum_h P[i, h] * feat_list[start + h][i] with P the reference's softmax(sigmoid(scores))
+    (LearnableWeightedMessageOp's gate / ori_ref / jk), differentiable once in `weight` ([1, in_dim]) and
+    `bias` ([1]).  feat_list: float32 [n, d] tensors on one HIP device, none requiring grad (row strides
+    are free: column windows of wider panels pass as they are).  Raises if a fused kernel cannot run."""
+    start, end = _check(feat_list, start, end, kind, weight, bias)
+    return _HopAttention.apply(weight, bias, start, end, kind, *feat_list)
