@@ -583,6 +583,39 @@ int srg_csr_mirror(const int64_t* indptr, const int32_t* indices, const int64_t*
 int srg_csr_validate(const int64_t* indptr, const int32_t* indices, int64_t n_rows,
                      int64_t nnz, int64_t n_cols, void* stream);
 
+/* ---- the sparse wavelet basis built on the device ---------------------------------------------------
+ * SpectralModel.calculate_wavelet + normalize_matrices (SSRG/models/base_scalable/base_model.py:236-265,
+ * 287-290) from the filter's dense output (srg_cheby_step_f64's R) to the L1-normalised CSR basis, without
+ * the dense block leaving the device: threshold + compact per block (count, prefix sum by the caller,
+ * fill), the blocks' rows appended (sp.hstack(blocks).tocsr()), sklearn's normalize(norm='l1') in place.
+ * Every result is bit for bit the reference's; nothing is added atomically: run-to-run identical. */
+
+/* Threshold and compact a dense fp64 block R [n_rows, w] (row stride ldr >= w, in elements; a column
+ * window of a wider panel is fine) that holds columns col0 .. col0 + w - 1 of the matrix
+ * (sub[sub < tol] = 0; csr_matrix(sub.astype(float32))): entry (i, c) survives iff
+ *   !(R[i,c] < tolerance)  &&  (float)R[i,c] != 0.0f
+ * -- a NaN entry and a NaN tolerance keep the entry (numpy's mask), -0 and fp64 values that round to fp32
+ * zero are dropped, values that round to an fp32 subnormal are kept, +-Inf follow the comparison.  It is
+ * stored as (float)R[i,c] (round to nearest even) with column id col0 + c, columns ascending in the row.
+ * Two passes over the same arguments, as srg_spgemm_f32: phase 0 writes cnt[r] = survivors of row r (int64
+ * [n_rows]); the caller forms ptr (the exclusive prefix sum of cnt) and allocates idx / val; phase 1 writes
+ * row r's survivors at ptr[r] .. of idx / val.  The same bits whether the 16-byte path (R on 16 bytes,
+ * ldr even) or the 8-byte path runs.  n_rows == 0 or w == 0 launches nothing; ldr < w, col0 < 0,
+ * col0 + w > INT32_MAX or another phase: SRG_ERR_INVALID.  Asynchronous on `stream`. */
+int srg_dense_sparsify_f64(int phase, const double* R, int64_t ldr, int64_t n_rows, int32_t w, double tolerance,
+                           int32_t col0, int64_t* cnt, const int64_t* ptr, int32_t* idx, float* val, void* stream);
+/* Appends the rows of one block's CSR to a CSR under construction: row r's entries
+ * src_idx / src_val[src_ptr[r] .. src_ptr[r+1]) are copied to dst_idx / dst_val at cursor[r], then
+ * cursor[r] += their count (cursor: int64 [n_rows], initially the final indptr[:-1]).  Calls on one stream
+ * append in call order, so a row's entries follow block order: the hstack.  Asynchronous on `stream`. */
+int srg_csr_append_rows_f32(const int64_t* src_ptr, const int32_t* src_idx, const float* src_val, int64_t n_rows,
+                            int64_t* cursor, int32_t* dst_idx, float* dst_val, void* stream);
+/* sklearn.preprocessing.normalize(M, norm='l1', axis=1) in place (_inplace_csr_row_normalize_l1): per
+ * row, acc = the fp64 sum of |x| over the stored entries, left to right from +0 (one sequential chain);
+ * if acc != 0 every value becomes (float)((double)x / acc), else the row is left as it is; a NaN acc is
+ * != 0, so the row becomes NaN.  indptr: int64 [n_rows + 1].  Asynchronous on `stream`. */
+int srg_csr_row_normalize_l1_f32(const int64_t* indptr, float* values, int64_t n_rows, void* stream);
+
 /* ---- sparse x sparse: the wavelet model's phi * phi^-1 (torch_sparse.spspmm / spmm) ------------------
  * SpectralModel.preprocess (SSRG/models/base_scalable/base_model.py:208-219) multiplies the two sparse
  * wavelet bases with torch_sparse.spspmm and the product into the features with torch_sparse.spmm

@@ -25,19 +25,6 @@ namespace {
 constexpr int64_t kSegShort = 64;
 
 template <typename T>
-__device__ __forceinline__ T bcast_lane(T v, int q)
-{
-    if constexpr (sizeof(T) == 8) {
-        const unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
-        const unsigned lo = __builtin_amdgcn_readlane((unsigned)bits, q);
-        const unsigned hi = __builtin_amdgcn_readlane((unsigned)(bits >> 32), q);
-        return __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
-    } else {
-        return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), q));
-    }
-}
-
-template <typename T>
 __global__ void __launch_bounds__(256)
 k_segment_sum(const int64_t* __restrict__ seg_ptr, const T* __restrict__ vals, int64_t n_seg,
               T* __restrict__ out)

@@ -98,6 +98,20 @@ template <typename T, int VEC> __device__ __forceinline__ typename Vec<T, VEC>::
     return z;
 }
 
+// Lane q's value in every lane (q wave-uniform): v_readlane, both halves of a 64-bit value.
+template <typename T>
+__device__ __forceinline__ T bcast_lane(T v, int q)
+{
+    if constexpr (sizeof(T) == 8) {
+        const unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
+        const unsigned lo = __builtin_amdgcn_readlane((unsigned)bits, q);
+        const unsigned hi = __builtin_amdgcn_readlane((unsigned)(bits >> 32), q);
+        return __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
+    } else {
+        return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), q));
+    }
+}
+
 constexpr int kWavesPerBlock = 4;   // 256-thread workgroups
 constexpr int kBlock = 64 * kWavesPerBlock;
 

@@ -18,6 +18,10 @@ load-balanced SpMM (slice waves, hub workgroups) plus srg_cheby_epilogue_f32 -- 
 the fused kernel -- and the panel can be filtered in column blocks (`col_block`) so that
 billion-edge graphs with d = 256 fit in HBM (R is written in place, no block copies).
 
+wavelet_basis_device / spectral_features_device assemble the thresholded, L1-normalised bases on the
+device as well (srg_dense_sparsify_f64, srg_csr_append_rows_f32, srg_csr_row_normalize_l1_f32: the
+filter's dense blocks never reach the host), bit for bit wavelet_basis / spectral_features.
+
 pygsp is not available offline: the restatement follows pygsp 0.5.x semantics.  phi and phi^-1 are
 bit-identical to the reference's own SpectralModel.preprocess run with pygsp restated
 (tests/golden/wav_*.npz) and validated against a dense eigendecomposition.  lmax is an
@@ -436,6 +440,83 @@ def wavelet_basis(adj: sp.spmatrix, scale: float = 0.5, order: int = 3, toleranc
     return out[0], out[1], filt.lmax
 
 
+class DeviceBasis:
+    """One wavelet basis as a CSR of device tensors: indptr int64 [n + 1], indices int32, values fp32."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor, n: int):
+        self.indptr, self.indices, self.values, self.n = indptr, indices, values, int(n)
+
+    def to_scipy(self) -> sp.csr_matrix:
+        return sp.csr_matrix((self.values.cpu().numpy(), self.indices.cpu().numpy(), self.indptr.cpu().numpy()),
+                             shape=(self.n, self.n))
+
+
+def sparsify_block(R: torch.Tensor, tolerance: float, col0: int):
+    """The block-local CSR of a dense fp64 device block R [n, w] holding columns col0 .. col0 + w - 1
+    (sub[sub < tolerance] = 0; csr_matrix(sub.astype(float32)), base_model.py:251-254) without the
+    block leaving the device: srg_dense_sparsify_f64 counts, torch.cumsum gives the row pointers, one
+    host scalar sizes the arrays, the second pass fills them.  Returns (cnt [n], ptr [n + 1], idx, val)."""
+    if not R.is_cuda or R.dim() != 2 or R.dtype != torch.float64 or R.stride(1) != 1:
+        raise ValueError("R must be a [n, w] fp64 device block with unit column stride")
+    n, w = R.shape
+    dev, st = R.device, _lib.stream(R.device)
+    cnt = torch.zeros(n, dtype=torch.int64, device=dev)
+    _lib.call(dev, "srg_dense_sparsify_f64", 0, R.data_ptr(), R.stride(0), n, w, float(tolerance), int(col0),
+              cnt.data_ptr(), None, None, None, st)
+    ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(cnt, 0, out=ptr[1:])
+    nnz = int(ptr[-1].item())
+    idx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    val = torch.empty(nnz, dtype=torch.float32, device=dev)
+    _lib.call(dev, "srg_dense_sparsify_f64", 1, R.data_ptr(), R.stride(0), n, w, float(tolerance), int(col0),
+              None, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), st)
+    return cnt, ptr, idx, val
+
+
+def hstack_normalize_blocks(blocks, counts: torch.Tensor) -> DeviceBasis:
+    """normalize(sp.hstack(blocks).tocsr(), norm='l1', axis=1) (base_model.py:257, 287-290) of block-local
+    device CSRs (ptr, idx, val) over the same n rows, `counts` their summed row counts: one
+    srg_csr_append_rows_f32 per block in block order, then srg_csr_row_normalize_l1_f32 in place."""
+    n = counts.numel()
+    dev, st = counts.device, _lib.stream(counts.device)
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=indptr[1:])
+    nnz = int(indptr[-1].item())
+    indices = torch.empty(nnz, dtype=torch.int32, device=dev)
+    values = torch.empty(nnz, dtype=torch.float32, device=dev)
+    cursor = indptr[:-1].clone()
+    for ptr, idx, val in blocks:
+        _lib.call(dev, "srg_csr_append_rows_f32", ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), n,
+                  cursor.data_ptr(), indices.data_ptr(), values.data_ptr(), st)
+    _lib.call(dev, "srg_csr_row_normalize_l1_f32", indptr.data_ptr(), values.data_ptr(), n, st)
+    return DeviceBasis(indptr, indices, values, n)
+
+
+def wavelet_basis_device(adj: sp.spmatrix, scale: float = 0.5, order: int = 3, tolerance: float = 1e-4,
+                         lmax: float | None = None, batch: int = 1000, device=None):
+    """wavelet_basis with the basis assembled on the device: the same filter calls, then per block and
+    scale threshold + compact (sparsify_block), and after the last block the append and the L1
+    normalisation (hstack_normalize_blocks).  Returns (phi, phi_inv, lmax) with phi / phi_inv as
+    DeviceBasis, bit for bit wavelet_basis's matrices; the only device-to-host traffic is one array
+    size per block and scale."""
+    L = laplacian_from_adj(adj)
+    filt = HeatWaveletFilter(L, [-scale, scale], order=order, lmax=lmax, device=device)
+    n = L.shape[0]
+    blocks = [[], []]
+    counts = [torch.zeros(n, dtype=torch.int64, device=filt.device) for _ in range(2)]
+    for c0 in range(0, n, batch):
+        w = min(batch, n - c0)
+        S = torch.zeros((n, w), dtype=torch.float64, device=filt.device)
+        S[torch.arange(c0, c0 + w, device=filt.device), torch.arange(w, device=filt.device)] = 1.0
+        R = filt.apply(S)
+        for s in range(2):
+            cnt, ptr, idx, val = sparsify_block(R[s], tolerance, c0)
+            counts[s] += cnt
+            blocks[s].append((ptr, idx, val))
+    phi, phi_inv = (hstack_normalize_blocks(blocks[s], counts[s]) for s in range(2))
+    return phi, phi_inv, filt.lmax
+
+
 def l1_normalize_rows(phi: sp.csr_matrix, device=None) -> sp.csr_matrix:
     """sklearn.preprocessing.normalize(phi, norm='l1', axis=1) (base_model.py:287-290) on the GPU:
     per row, the fp64 sum of |x| left to right (srg_segment_sum_f64), then x / sum in fp64
@@ -474,3 +555,19 @@ def spectral_features(adj: sp.spmatrix, feature, scale: float = 0.5, order: int 
     A_phi = DeviceCSR.from_scipy(phi, device=dev)
     loc = torch.relu(spmm(A_phi, spmm(A_inv, X.to(dev).contiguous())))
     return torch.cat((X, loc.cpu()), dim=1), phi, phi_inv, lmax
+
+
+def spectral_features_device(adj: sp.spmatrix, feature, scale: float = 0.5, order: int = 3, tolerance: float = 1e-4,
+                             lmax: float | None = None, batch: int = 1000, device=None):
+    """spectral_features with the bases built and kept on the device (wavelet_basis_device): the same
+    two SpMMs over the same CSRs, so [X | relu(phi (phi^-1 X))] is the same bits, as a device float32
+    tensor; phi / phi_inv are DeviceBasis."""
+    from .csr import DeviceCSR
+    from .spmm import spmm
+    phi, phi_inv, lmax = wavelet_basis_device(adj, scale, order, tolerance, lmax, batch, device)
+    dev = phi.indptr.device
+    X = torch.as_tensor(np.asarray(feature, dtype=np.float32)).to(dev).contiguous()
+    A_inv = DeviceCSR.from_tensors(phi_inv.indptr, phi_inv.indices, phi_inv.values, n_cols=phi_inv.n, device=dev)
+    A_phi = DeviceCSR.from_tensors(phi.indptr, phi.indices, phi.values, n_cols=phi.n, device=dev)
+    loc = torch.relu(spmm(A_phi, spmm(A_inv, X)))
+    return torch.cat((X, loc), dim=1), phi, phi_inv, lmax
