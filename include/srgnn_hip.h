@@ -478,6 +478,53 @@ int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int3
                             int kind, const float* dzflat, float* dw, float* db, void* scratch, int64_t n,
                             int32_t d, void* stream);
 
+/* GAMLP's recursive hop attention (SSRG/operators/message_operator/iterate_learnable_weighted_message_op.py,
+ * combination type recursive), forward and backward, without the reference's H^2 panel-sized steps
+ * (DESIGN.md §5.4.3).  panels / ldp / T as above; the hops used are panels 0 .. end-1 (H = end, 1 <= end <= T:
+ * the reference works with start == 0 only); w = [w_h | w_c] is the weight row of Linear(2d, 1) (w_h meets
+ * the hop, w_c the running combination), b its bias.  With p_j = w_h . F_j[i, :] and q_j = w_c . F_j[i, :], per
+ * row i:  W(0) = [1];  for k = 1 .. H-1:  r = sum_{j<k} W(k-1)_j q_j,  s = (p_k + r) + b,  g_k = 1 / (1 + expf(-s)),
+ * W(k) = softmax([W(k-1)_0 .. W(k-1)_{k-1}, g_k]) (the reference re-softmaxes weights that were softmaxed
+ * already; kept);  out[i, :] = sum_j W(H-1)_j F_j[i, :].  Asynchronous on `stream`, deterministic (no atomics;
+ * the bits depend on the shapes and the panels' alignment only), within the bound of DESIGN.md §5.4.3 of the
+ * formula evaluated exactly.  n == 0 is a no-op.
+ * Scores, hop-major: zp[h*n + i] = p_h, zq[h*n + i] = q_h for h = 0 .. H-1: srg_hop_scores_f32's lane layout,
+ * per panel row two fma chains per lane from +0 in chunk order (w[0:d] and w[d:2d]) from one load, one xor
+ * butterfly each.  The bias is not added here. */
+int srg_hop_recur_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* w,
+                             float* zp, float* zq, int64_t n, int32_t d, void* stream);
+/* Attend: the recurrence above, one thread per row: r = W_0*q_0 + W_1*q_1 + ... left to right with separate
+ * multiply and add, s = (p_k + r) + b, g_k = 1 / (1 + expf(-s)), e_j = expf(W(k-1)_j), e_k = expf(g_k),
+ * W(k)_j = e_j / (e_0 + e_1 + ... + e_k) (the sum left to right; every add, multiply and divide correctly
+ * rounded; the arguments lie in (0, 1], so no row maximum is subtracted).  P [n, H] contiguous receives W(H-1);
+ * out[i, :] = P[i,0]*F_0[i, :] + P[i,1]*F_1[i, :] + ... left to right with separate multiply and add (out: [n, d],
+ * leading dimension ldo, no alias of a panel 0 .. end-1).  work: (H (H+1) / 2 + H) * n floats kept for the
+ * backward, as vectors of n: vector k (k+1) / 2 + j holds W(k)_j (j <= k), vector H (H+1) / 2 + k holds g_k.
+ * H = 1 gives P = 1 and out = the panel's bits. */
+int srg_hop_recur_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* zp,
+                             const float* zq, const float* b, float* work, float* P, float* out, int64_t ldo,
+                             int64_t n, int32_t d, void* stream);
+/* Attend gradient for G = dL/dout [n, d] (leading dimension ldg): dW(H-1)_j = G[i, :] . F_j[i, :] (the scores'
+ * lane layout: one fma chain per lane from +0, the butterfly), then per row, for k = H-1 .. 1:
+ *   t = W(k)_0*dW_0 + ... + W(k)_k*dW_k (left to right)     dx_j = W(k)_j * (dW_j - t)
+ *   ds = dx_k * (g_k * (1 - g_k))                            dzp[k*n + i] = ds
+ *   dzq[j*n + i] += ds * W(k-1)_j,   dW(k-1)_j = dx_j + ds * q_j      for j < k
+ * (a dzq's first term stored as it is, the later ones added in descending k; dzp[0*n + i] = 0,
+ * dzq[(H-1)*n + i] = 0).  zq and work as the forward left them; dzp, dzq: [H*n], no alias of each other or zq. */
+int srg_hop_recur_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
+                                  const float* G, int64_t ldg, const float* zq, const float* work, float* dzp,
+                                  float* dzq, int64_t n, int32_t d, void* stream);
+/* Parameter gradient: dw [2d] = [sum_i sum_h dzp[h,i] F_h[i, :] | sum_i sum_h dzq[h,i] F_h[i, :]] and
+ * db [1] = sum_i s[i], s[i] = dzp[0,i] + dzp[1,i] + ... (left to right); either may be NULL: not computed.
+ * srg_hop_scores_grad_f32's two stages and its rpg: per group, panel and column two fma chains from +0 over the
+ * rows ascending from one load, fma(dzp[h,i], F_h[i,c], .) and fma(dzq[h,i], F_h[i,c], .), each kind added over
+ * h ascending; stage 2 adds the groups' partials in group order.  `scratch`: device, 16-byte aligned,
+ * srg_hop_recur_scores_grad_scratch_bytes() bytes.  n == 0 stores zeros. */
+int srg_hop_recur_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t H, int64_t* bytes);
+int srg_hop_recur_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
+                                  const float* dzp, const float* dzq, float* dw, float* db, void* scratch, int64_t n,
+                                  int32_t d, void* stream);
+
 /* srg_spmm_csr_f32 with the aggregation step fused into its epilogue: Y = A*X as above and, for
  * every element y stored, agg = (agg_init ? 0 : agg) + w*y (separate multiply / add) -- the same
  * result as srg_spmm_csr_f32 followed by srg_hop_accumulate_f32(INIT or ADD), one panel pass less.

@@ -1,7 +1,9 @@
 // srg_hopattn.hip -- the learnable hop attention of GAMLP (SSRG/operators/message_operator/
 // learnable_weighted_messahe_op.py, combination types gate / ori_ref / jk), forward and backward, without
 // the [H*n, (T+1)*d] panel the reference's torch composition builds: scores, attend, attend gradient and
-// the parameter gradient, each a streaming pass over the hop panels.
+// the parameter gradient, each a streaming pass over the hop panels; and the recursive
+// attention of iterate_learnable_weighted_message_op.py, the same four steps around a scalar recurrence per
+// row (the srg_hop_recur_* entries).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -156,8 +158,8 @@ k_hop_combine(HopPanels pl, int start, int H, const float* __restrict__ P, float
 }
 
 // dP[i, h] = G[i, :] . F_{start+h}[i, :]: the scores' lane layout, one fma chain per lane from +0 in chunk
-// order, xor butterfly.
-template <int VEC>
+// order, xor butterfly.  HOP_MAJOR stores dP[h * n + i] (the recursive attention's per-row vectors).
+template <int VEC, bool HOP_MAJOR = false>
 __global__ void __launch_bounds__(256)
 k_hop_rowdots(HopPanels pl, int start, int H, const float* __restrict__ G, int64_t ldg, float* __restrict__ dP,
               int64_t n, int cpr, int lgS)
@@ -182,7 +184,7 @@ k_hop_rowdots(HopPanels pl, int start, int H, const float* __restrict__ G, int64
                 for (int j = 0; j < VEC; ++j) dot = __builtin_fmaf(elem(gc, j), elem(xc, j), dot);
             }
             for (int m = S >> 1; m > 0; m >>= 1) dot = __fadd_rn(dot, __shfl_xor(dot, m));
-            if (live && c0 == (h & (S - 1))) dP[r * H + h] = dot;
+            if (live && c0 == (h & (S - 1))) dP[HOP_MAJOR ? (int64_t)h * n + r : r * H + h] = dot;
         }
     }
 }
@@ -301,6 +303,240 @@ k_hop_wgrad_fold(const float* __restrict__ partials, int64_t n_groups, int in_di
 }
 
 // ------------------------------------------------------------------------------------------------
+// The recursive hop attention (IterateLearnableWeightedMessageOp).  w = [w_h | w_c] is the
+// row of Linear(2d, 1); w_c . (sum_j W_j F_j[i, :]) = sum_j W_j (w_c . F_j[i, :]), so between the panels and
+// the final weighted sum the operator is a scalar recurrence per row on the 2H dot products below.
+//
+// zp[h * n + i] = w_h . F_h[i, :], zq[h * n + i] = w_c . F_h[i, :]: k_hop_rowdots' lane layout, two fma
+// chains per lane from +0 in chunk order from one load of the panel row, one butterfly each.
+// ------------------------------------------------------------------------------------------------
+template <int VEC>
+__global__ void __launch_bounds__(256)
+k_hop_recur_scores(HopPanels pl, int H, const float* __restrict__ w, float* __restrict__ zp, float* __restrict__ zq,
+                   int64_t n, int d, int cpr, int lgS)
+{
+    typedef typename Vec<float, VEC>::type V;
+    const int S = 1 << lgS, R = 64 >> lgS;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> lgS, c0 = lane & (S - 1);
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const float* wc = w + d;
+    for (int64_t base = wave * R; base < n; base += waves * R) {
+        const int64_t r = base + g;
+        const bool live = r < n;
+        for (int h = 0; h < H; ++h) {
+            const float* xr = pl.p[h] + r * pl.ld[h];
+            float p = 0.0f, q = 0.0f;
+            for (int c = c0; live && c < cpr; c += S) {
+                const V xc = vload<float, VEC>(xr + (int64_t)c * VEC);
+                const V hc = vload<float, VEC>(w + (int64_t)c * VEC);
+                const V cc = vload<float, VEC>(wc + (int64_t)c * VEC);
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    p = __builtin_fmaf(elem(hc, j), elem(xc, j), p);
+                    q = __builtin_fmaf(elem(cc, j), elem(xc, j), q);
+                }
+            }
+            for (int m = S >> 1; m > 0; m >>= 1) {
+                p = __fadd_rn(p, __shfl_xor(p, m));
+                q = __fadd_rn(q, __shfl_xor(q, m));
+            }
+            if (live && c0 == (h & (S - 1))) {
+                zp[(int64_t)h * n + r] = p;
+                zq[(int64_t)h * n + r] = q;
+            }
+        }
+    }
+}
+
+// The work buffer of the recurrence, (H (H + 1) / 2 + H) vectors of n floats: vector tri(i) + j holds
+// W(i)_j, the weights after step i (j <= i), vector H (H + 1) / 2 + i holds g_i.  A thread owns a row and
+// walks the vectors at stride n, so a wave's accesses are 64 consecutive floats.  While a row is worked on
+// its H-vectors live in LDS, a column of RECUR_BLOCK-strided floats per thread (no two threads share a
+// word, so no barrier): a private array under a runtime index would go to scratch, and walking the
+// recurrence through the global buffer alone made every step wait for its own stores and loads
+// (k_hop_recur_forward 77 -> 31 us, k_hop_recur_backward 97 -> 70 us at n = 200,000, H = 11).
+__host__ __device__ __forceinline__ int64_t tri(int i) { return (int64_t)i * (i + 1) / 2; }
+constexpr int RECUR_BLOCK = 64;
+constexpr int RECUR_FWD_VECTORS = 3;   // p, q, W
+constexpr int RECUR_BWD_VECTORS = 5;   // q, dW, dq, W(i), W(i-1)
+
+// count floats src[j * n] -> dst[j * RECUR_BLOCK] (a thread's column of an LDS vector), eight loads in flight at a
+// time: a loop of single loads would wait out one memory latency per element.  The tail batch reads the last
+// element again instead of branching.
+__device__ __forceinline__ void recur_fetch(float* dst, const float* __restrict__ src, int64_t n, int count)
+{
+    for (int j0 = 0; j0 < count; j0 += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[(int64_t)(j0 + u < count ? j0 + u : count - 1) * n];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (j0 + u < count) dst[(j0 + u) * RECUR_BLOCK] = v[u];
+    }
+}
+
+// One thread per row.  W(0) = [1]; for i = 1 .. H-1, with W = W(i-1):
+//   r = W_0 q_0 + W_1 q_1 + ... + W_{i-1} q_{i-1}   (left to right)       s = (p_i + r) + b
+//   g_i = 1 / (1 + expf(-s))
+//   e_j = expf(W_j) (j < i), e_i = expf(g_i),  W(i)_j = e_j / (e_0 + e_1 + ... + e_i)   (left to right)
+// every add, multiply and divide correctly rounded; the arguments of expf lie in (0, 1], so no maximum is
+// subtracted.  P[i, :] = W(H-1).  Dynamic LDS: RECUR_FWD_VECTORS * H * RECUR_BLOCK floats.
+__global__ void __launch_bounds__(RECUR_BLOCK)
+k_hop_recur_forward(const float* __restrict__ zp, const float* __restrict__ zq, const float* __restrict__ b,
+                    float* __restrict__ work, float* __restrict__ P, int64_t n, int H)
+{
+    extern __shared__ float recur_lds[];
+    float* sp = recur_lds + threadIdx.x;            // element j at [j * RECUR_BLOCK]
+    float* sq = sp + H * RECUR_BLOCK;
+    float* sw = sq + H * RECUR_BLOCK;
+    const int64_t stride = (int64_t)gridDim.x * RECUR_BLOCK;
+    const float bias = b[0];
+    for (int64_t r = (int64_t)blockIdx.x * RECUR_BLOCK + threadIdx.x; r < n; r += stride) {
+        float* wr = work + r;
+        float* gs = wr + (tri(H - 1) + H) * n;
+        recur_fetch(sp, zp + r, n, H);
+        recur_fetch(sq, zq + r, n, H);
+        sw[0] = 1.0f;
+        wr[0] = 1.0f;
+        gs[0] = 0.0f;   // g_0 never matters: a one-column softmax is 1
+        for (int i = 1; i < H; ++i) {
+            float* cur = wr + tri(i) * n;
+            float rs = 0.0f, sum = 0.0f;
+            for (int j = 0; j < i; ++j) {
+                const float wj = sw[j * RECUR_BLOCK];
+                const float m = __fmul_rn(wj, sq[j * RECUR_BLOCK]);
+                const float e = expf(wj);
+                rs = j == 0 ? m : __fadd_rn(rs, m);
+                sum = j == 0 ? e : __fadd_rn(sum, e);
+                sw[j * RECUR_BLOCK] = e;
+            }
+            const float s = __fadd_rn(__fadd_rn(sp[i * RECUR_BLOCK], rs), bias);
+            const float gi = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-s)));
+            const float eg = expf(gi);
+            sum = __fadd_rn(sum, eg);
+            gs[(int64_t)i * n] = gi;
+            sw[i * RECUR_BLOCK] = eg;
+            for (int j = 0; j <= i; ++j) {
+                const float wj = __fdiv_rn(sw[j * RECUR_BLOCK], sum);
+                sw[j * RECUR_BLOCK] = wj;
+                cur[(int64_t)j * n] = wj;
+            }
+        }
+        for (int j = 0; j < H; ++j) P[r * H + j] = sw[j * RECUR_BLOCK];
+    }
+}
+
+// The reverse recurrence, one thread per row.  dzp holds dW(H-1)_j = G[i, :] . F_j[i, :] on entry (hop-major);
+// for i = H-1 .. 1, with W = W(i), dW = dW(i):
+//   t = W_0 dW_0 + ... + W_i dW_i (left to right)      dx_j = W_j (dW_j - t)
+//   ds = dx_i * (g_i * (1 - g_i))                      dzp[i] = ds
+//   dzq[j] (+)= ds * W(i-1)_j,  dW(i-1)_j = dx_j + ds * q_j   for j < i
+// dzq[j]'s first term (i = H-1) is stored as it is and the later ones added in descending i; dzq[H-1] = 0,
+// dzp[0] = 0.  Slot i of dW is dead after step i, which is where ds goes.  Dynamic LDS: RECUR_BWD_VECTORS * H *
+// RECUR_BLOCK floats.
+__global__ void __launch_bounds__(RECUR_BLOCK)
+k_hop_recur_backward(const float* __restrict__ zq, const float* __restrict__ work, float* __restrict__ dzp,
+                     float* __restrict__ dzq, int64_t n, int H)
+{
+    extern __shared__ float recur_lds[];
+    float* sq = recur_lds + threadIdx.x;            // element j at [j * RECUR_BLOCK]
+    float* sdw = sq + H * RECUR_BLOCK;
+    float* sdq = sdw + H * RECUR_BLOCK;
+    float* swc = sdq + H * RECUR_BLOCK;
+    float* swp = swc + H * RECUR_BLOCK;
+    const int64_t stride = (int64_t)gridDim.x * RECUR_BLOCK;
+    for (int64_t r = (int64_t)blockIdx.x * RECUR_BLOCK + threadIdx.x; r < n; r += stride) {
+        const float* wr = work + r;
+        const float* gs = wr + (tri(H - 1) + H) * n;
+        recur_fetch(sq, zq + r, n, H);
+        recur_fetch(sdw, dzp + r, n, H);
+        recur_fetch(swc, wr + tri(H - 1) * n, n, H);
+        sdq[(H - 1) * RECUR_BLOCK] = 0.0f;
+        for (int i = H - 1; i >= 1; --i) {
+            // swc holds W(i): loaded above for i = H-1, the W(i-1) of the step before otherwise
+            const float* prev = wr + tri(i - 1) * n;
+            const float gi = gs[(int64_t)i * n];
+            recur_fetch(swp, prev, n, i);
+            float t = 0.0f;
+            for (int j = 0; j <= i; ++j) {
+                const float m = __fmul_rn(swc[j * RECUR_BLOCK], sdw[j * RECUR_BLOCK]);
+                t = j == 0 ? m : __fadd_rn(t, m);
+            }
+            const float dxi = __fmul_rn(swc[i * RECUR_BLOCK], __fsub_rn(sdw[i * RECUR_BLOCK], t));
+            const float ds = __fmul_rn(dxi, __fmul_rn(gi, __fsub_rn(1.0f, gi)));
+            for (int j = 0; j < i; ++j) {
+                const float dx = __fmul_rn(swc[j * RECUR_BLOCK], __fsub_rn(sdw[j * RECUR_BLOCK], t));
+                const float m = __fmul_rn(ds, swp[j * RECUR_BLOCK]);
+                sdq[j * RECUR_BLOCK] = i == H - 1 ? m : __fadd_rn(sdq[j * RECUR_BLOCK], m);
+                sdw[j * RECUR_BLOCK] = __fadd_rn(dx, __fmul_rn(ds, sq[j * RECUR_BLOCK]));
+            }
+            sdw[i * RECUR_BLOCK] = ds;
+            float* x = swc; swc = swp; swp = x;
+        }
+        sdw[0] = 0.0f;
+        for (int j = 0; j < H; ++j) {
+            dzp[(int64_t)j * n + r] = sdw[j * RECUR_BLOCK];
+            dzq[(int64_t)j * n + r] = sdq[j * RECUR_BLOCK];
+        }
+    }
+}
+
+// Parameter gradient of the recursive attention, stage 1: k_hop_wgrad_partial's groups, tiles and rows-
+// ascending fma chains, two chains per panel and column from one load,
+//   hp_h[c] = fma(dzp[h, i], F_h[i, c], hp_h[c])      cp_h[c] = fma(dzq[h, i], F_h[i, c], cp_h[c])
+// each kind added over h ascending (the first as it is) into partials[q, c] and partials[q, d + c]; the
+// group's bias part s[i0] + s[i0+1] + ... (s[i] = dzp[0, i] + dzp[1, i] + ...) goes to partials[q, 2d].
+template <int VEC>
+__global__ void __launch_bounds__(256)
+k_hop_recur_wgrad_partial(HopPanels pl, int H, const float* __restrict__ dzp, const float* __restrict__ dzq,
+                          const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d, int cpr,
+                          int lgCT, int64_t rpg, int64_t n_groups, int want_w)
+{
+    typedef typename Vec<float, VEC>::type V;
+    const int CT = 1 << lgCT;
+    const int c0 = threadIdx.x & (CT - 1);
+    const int64_t q = (int64_t)blockIdx.x * (256 >> lgCT) + (threadIdx.x >> lgCT);
+    if (q >= n_groups) return;
+    const int c = blockIdx.y * CT + c0;
+    const int64_t ldq = pad4((int64_t)2 * d + 1);
+    float* out = partials + q * ldq;
+    const int64_t i0 = q * rpg, i1 = i0 + rpg < n ? i0 + rpg : n;
+    if (c == 0) {
+        float t = s[i0];
+        for (int64_t i = i0 + 1; i < i1; ++i) t = __fadd_rn(t, s[i]);
+        out[2 * d] = t;
+    }
+    if (!want_w || c >= cpr) return;
+    V toth, totc;
+    for (int h = 0; h < H; ++h) {
+        const float* x = pl.p[h] + (int64_t)c * VEC;
+        const int64_t ldx = pl.ld[h];
+        const float* dp = dzp + (int64_t)h * n;
+        const float* dq = dzq + (int64_t)h * n;
+        V ha = vzero<float, VEC>(), ca = vzero<float, VEC>();
+#pragma unroll 4
+        for (int64_t i = i0; i < i1; ++i) {
+            const V xc = vload<float, VEC>(x + i * ldx);
+            const float pi = dp[i], qi = dq[i];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
+                elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            elem(toth, j) = h == 0 ? elem(ha, j) : __fadd_rn(elem(toth, j), elem(ha, j));
+            elem(totc, j) = h == 0 ? elem(ca, j) : __fadd_rn(elem(totc, j), elem(ca, j));
+        }
+    }
+    vstore<float, VEC>(out + (int64_t)c * VEC, toth, false);
+    vstore<float, VEC>(out + d + (int64_t)c * VEC, totc, false);
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 struct HopShape {
@@ -356,6 +592,9 @@ int hop_shape(const float* const* panels, const int64_t* ldp, int T, int start, 
     hs.thread_blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 256 * 16);
     return SRG_OK;
 }
+
+// the recurrence kernels' grid: one wave per block, grid-stride over the rows
+unsigned recur_blocks(int64_t n) { return (unsigned)std::min<int64_t>((n + RECUR_BLOCK - 1) / RECUR_BLOCK, 256 * 64); }
 
 int check_kind(int kind)
 {
@@ -496,6 +735,124 @@ int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int3
 #define LAUNCH(V) hipLaunchKernelGGL((k_hop_wgrad_partial<V>), grid, dim3(256), 0, st, hs.pl, T, start, H, kind, dzflat, \
                                      s, partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr)
     SRG_HOP_BY_VEC(vec, LAUNCH);
+#undef LAUNCH
+    hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials,
+                       n_groups, in_dim, dw, db);
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+// ---- the recursive attention (start == 0: the reference works with no other) ----
+
+int srg_hop_recur_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* w,
+                             float* zp, float* zq, int64_t n, int32_t d, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    HopShape hs;
+    const void* wide[] = {w};
+    const int64_t wide_ld[] = {0};
+    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, wide, wide_ld, 1, hs)) return rc;
+    if (n == 0) return srg_ok();
+    if (!zp || !zq || zp == zq) return srg_fail(SRG_ERR_INVALID, "zp / zq null or the same");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_recur_scores<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, end, w, zp, \
+                                     zq, n, d, hs.cpr, hs.lgS)
+    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#undef LAUNCH
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_hop_recur_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* zp,
+                             const float* zq, const float* b, float* work, float* P, float* out, int64_t ldo,
+                             int64_t n, int32_t d, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    HopShape hs;
+    const void* wide[] = {out};
+    const int64_t wide_ld[] = {ldo};
+    if (ldo < d) return srg_fail(SRG_ERR_INVALID, "ldo=%lld < d=%d", (long long)ldo, d);
+    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, wide, wide_ld, 1, hs)) return rc;
+    if (n == 0) return srg_ok();
+    if (!zp || !zq || !b || !work || !P) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    for (int t = 0; t < end; ++t)
+        if (out == panels[t]) return srg_fail(SRG_ERR_INVALID, "out must not alias a hop panel");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_hop_recur_forward, dim3(recur_blocks(n)), dim3(RECUR_BLOCK),
+                       (size_t)RECUR_FWD_VECTORS * end * RECUR_BLOCK * sizeof(float), st, zp, zq, b, work, P, n, end);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_combine<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, P, out, \
+                                     ldo, n, hs.cpr, hs.lgS)
+    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#undef LAUNCH
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_hop_recur_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
+                                  const float* G, int64_t ldg, const float* zq, const float* work, float* dzp,
+                                  float* dzq, int64_t n, int32_t d, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    HopShape hs;
+    const void* wide[] = {G};
+    const int64_t wide_ld[] = {ldg};
+    if (ldg < d) return srg_fail(SRG_ERR_INVALID, "ldg=%lld < d=%d", (long long)ldg, d);
+    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, wide, wide_ld, 1, hs)) return rc;
+    if (n == 0) return srg_ok();
+    if (!zq || !work || !dzp || !dzq) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    if (dzp == dzq || dzp == zq || dzq == zq) return srg_fail(SRG_ERR_INVALID, "dzp, dzq and zq must not alias");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_rowdots<V, true>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, G, \
+                                     ldg, dzp, n, hs.cpr, hs.lgS)
+    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#undef LAUNCH
+    hipLaunchKernelGGL(k_hop_recur_backward, dim3(recur_blocks(n)), dim3(RECUR_BLOCK),
+                       (size_t)RECUR_BWD_VECTORS * end * RECUR_BLOCK * sizeof(float), st, zq, work, dzp, dzq, n, end);
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
+}
+
+int srg_hop_recur_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t H, int64_t* bytes)
+{
+    if (!bytes) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    if (n < 0 || d < 1 || H < 1 || H > SRG_HOP_MAX || 2 * (int64_t)d + 1 > INT32_MAX)
+        return srg_fail(SRG_ERR_INVALID, "bad shape n=%lld d=%d H=%d", (long long)n, d, H);
+    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
+    // s [n], then partials [n_groups, 2d + 1], each row of either rounded up to 16 bytes
+    *bytes = (pad4(n) + n_groups * pad4((int64_t)2 * d + 1)) * (int64_t)sizeof(float);
+    return srg_ok();
+}
+
+int srg_hop_recur_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
+                                  const float* dzp, const float* dzq, float* dw, float* db, void* scratch, int64_t n,
+                                  int32_t d, void* stream)
+{
+    SRG_DEVICE_GUARD(stream);
+    HopShape hs;
+    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, nullptr, nullptr, 0, hs)) return rc;
+    if (!dw && !db) return srg_ok();
+    const int in_dim = 2 * d;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {   // empty sums
+        if (dw) SRG_HIP_CHECK(hipMemsetAsync(dw, 0, (size_t)in_dim * sizeof(float), st));
+        if (db) SRG_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float), st));
+        return srg_ok();
+    }
+    if (!dzp || !dzq || !scratch || !aligned(scratch, 16))
+        return srg_fail(SRG_ERR_INVALID, "dzp, dzq or scratch null, or scratch not 16-byte aligned");
+    const int cpr = hs.cpr;
+    int lgCT = 0;
+    while (lgCT < 8 && (1 << lgCT) < cpr) ++lgCT;
+    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
+    float* s = static_cast<float*>(scratch);
+    float* partials = s + pad4(n);
+    const int groups_per_block = 256 >> lgCT;
+    const dim3 grid((unsigned)((n_groups + groups_per_block - 1) / groups_per_block),
+                    (unsigned)((cpr + (1 << lgCT) - 1) >> lgCT));
+    hipLaunchKernelGGL(k_hop_dzsum, dim3(hs.thread_blocks), dim3(256), 0, st, dzp, s, n, end);
+#define LAUNCH(V) hipLaunchKernelGGL((k_hop_recur_wgrad_partial<V>), grid, dim3(256), 0, st, hs.pl, end, dzp, dzq, s, \
+                                     partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr)
+    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
 #undef LAUNCH
     hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials,
                        n_groups, in_dim, dw, db);

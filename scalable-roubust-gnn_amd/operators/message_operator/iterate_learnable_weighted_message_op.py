@@ -1,7 +1,14 @@
 """IterateLearnableWeightedMessageOp (SSRG/operators/message_operator/iterate_learnable_weighted_message_op.py:
 8-51): 'recursive' combination -- hop i's per-node weight comes from Linear(2 feat_dim, 1) on
 [hop i | the running combination], the weights so far are re-softmaxed, and the combination is
-rebuilt from hop `start` with them.  Same parameters and arithmetic order as the reference."""
+rebuilt from hop `start` with them.  Same parameters and arithmetic order as the reference.
+
+`fused` (default False): with it set, start == 0 and float32 hop tensors held on a HIP device, none of which
+requires grad, run srgnn.hop_attention.hop_attention_recursive (the device kernels of DESIGN.md §5.4.3: the same
+weights within a derived rounding bound, gradients for the Linear's weight and bias, two streaming passes and a
+scalar recurrence per row instead of (end - start)^2 panel-sized steps).  Everything else takes the composition
+below, unchanged -- the IndexError the reference raises for start >= 1 included.
+"""
 import torch
 import torch.nn.functional as F
 from torch.nn import Linear
@@ -19,8 +26,15 @@ class IterateLearnableWeightedMessageOp(MessageOp):
         if len(args) != 1:
             raise ValueError("Invalid parameter numbers for the recursive iterate weighted aggregator!")
         self.learnable_weight = Linear(2 * args[0], 1)
+        self.fused = False
 
     def combine(self, feat_list):
+        if (self.fused and self.start == 0 and isinstance(feat_list, (list, tuple)) and len(feat_list) > 0
+                and all(isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.float32 and not f.requires_grad
+                        for f in feat_list)):
+            from srgnn.hop_attention import hop_attention_recursive
+            return hop_attention_recursive(list(feat_list), self.end, self.learnable_weight.weight,
+                                           self.learnable_weight.bias)
         base = feat_list[self.start]
         combined = base
         weights = None

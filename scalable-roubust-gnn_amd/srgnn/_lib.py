@@ -108,6 +108,11 @@ EXPORTED_SYMBOLS = (
     "srg_hop_attend_grad_f32",
     "srg_hop_scores_grad_scratch_bytes",
     "srg_hop_scores_grad_f32",
+    "srg_hop_recur_scores_f32",
+    "srg_hop_recur_attend_f32",
+    "srg_hop_recur_attend_grad_f32",
+    "srg_hop_recur_scores_grad_scratch_bytes",
+    "srg_hop_recur_scores_grad_f32",
     "srg_spmm_agg_f32",
     "srg_spmm_span_f32",
     "srg_spmm_cheby_f32",
@@ -229,8 +234,15 @@ def _declare(lib):
                                             _i32, _p]
     lib.srg_hop_scores_grad_scratch_bytes.argtypes = [_i64, _i32, _i32, _i32, ctypes.c_int, ctypes.POINTER(_i64)]
     lib.srg_hop_scores_grad_f32.argtypes = [_p, _p, _i32, _i32, _i32, ctypes.c_int, _p, _p, _p, _p, _i64, _i32, _p]
+    lib.srg_hop_recur_scores_f32.argtypes = [_p, _p, _i32, _i32, _p, _p, _p, _i64, _i32, _p]
+    lib.srg_hop_recur_attend_f32.argtypes = [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _p]
+    lib.srg_hop_recur_attend_grad_f32.argtypes = [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _i64, _i32, _p]
+    lib.srg_hop_recur_scores_grad_scratch_bytes.argtypes = [_i64, _i32, _i32, ctypes.POINTER(_i64)]
+    lib.srg_hop_recur_scores_grad_f32.argtypes = [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i32, _p]
     for name in ("srg_hop_scores_f32", "srg_hop_attend_f32", "srg_hop_attend_grad_f32",
-                 "srg_hop_scores_grad_scratch_bytes", "srg_hop_scores_grad_f32"):
+                 "srg_hop_scores_grad_scratch_bytes", "srg_hop_scores_grad_f32",
+                 "srg_hop_recur_scores_f32", "srg_hop_recur_attend_f32", "srg_hop_recur_attend_grad_f32",
+                 "srg_hop_recur_scores_grad_scratch_bytes", "srg_hop_recur_scores_grad_f32"):
         getattr(lib, name).restype = ctypes.c_int
     lib.srg_tail_record_f32.argtypes = [_p, _p, _i64, _i32, _i64, _i32, _f32, _p]
     lib.srg_tail_record_f32.restype = ctypes.c_int

@@ -1,7 +1,11 @@
 """GAMLP's learnable hop attention on the device (LearnableWeightedMessageOp, combination types gate /
 ori_ref / jk): srg_hop_scores_f32 + srg_hop_attend_f32 forward, srg_hop_attend_grad_f32 +
 srg_hop_scores_grad_f32 backward, without the [H*n, (T+1)*d] panel of the torch composition
-(DESIGN.md §5.4.2).  The hop panels are precomputed constants: gradients go to the weight and the bias.
+(DESIGN.md §5.4.2); and the recursive attention (IterateLearnableWeightedMessageOp, combination type
+recursive): srg_hop_recur_scores_f32 + srg_hop_recur_attend_f32 forward, srg_hop_recur_attend_grad_f32 +
+srg_hop_recur_scores_grad_f32 backward, a scalar recurrence per row between two streaming passes instead of
+the composition's H^2 panel-sized steps.  The hop panels are precomputed constants:
+gradients go to the weight and the bias.
 """
 from __future__ import annotations
 
@@ -17,7 +21,7 @@ KINDS = {"gate": _lib.SRG_HOP_GATE, "ori_ref": _lib.SRG_HOP_ORI_REF, "jk": _lib.
 
 def in_dim(kind: str, T: int, d: int) -> int:
     """Input width of the operator's Linear for a list of T hops of d columns."""
-    return {"gate": d, "ori_ref": 2 * d, "jk": T * d + d}[kind]
+    return {"gate": d, "ori_ref": 2 * d, "jk": T * d + d, "recursive": 2 * d}[kind]
 
 
 def _pairing(kind: str) -> int:
@@ -32,9 +36,9 @@ def _panel_args(feats):
     return ptrs, lds
 
 
-def _check(feat_list, start, end, kind, weight, bias):
-    if kind not in KINDS:
-        raise ValueError(f"hop_attention: kind {kind!r} is not one of {sorted(KINDS)}")
+def _check(feat_list, start, end, kind, weight, bias, kinds=KINDS):
+    if kind not in kinds:
+        raise ValueError(f"hop_attention: kind {kind!r} is not one of {sorted(kinds)}")
     if not isinstance(feat_list, (list, tuple)) or len(feat_list) == 0:
         raise ValueError("hop_attention: feat_list must be a non-empty list of hop tensors")
     T = len(feat_list)
@@ -136,3 +140,71 @@ def hop_attention(feat_list, start, end, kind, weight, bias):
     are free: column windows of wider panels pass as they are).  Raises if a fused kernel cannot run."""
     start, end = _check(feat_list, start, end, kind, weight, bias)
     return _HopAttention.apply(weight, bias, start, end, kind, *feat_list)
+
+
+class _HopAttentionRecursive(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, bias, end, *feats):
+        dev = feats[0].device
+        n, d = feats[0].shape
+        T, H = len(feats), end
+        w = weight.detach().contiguous().view(-1)
+        b = bias.detach().contiguous().view(-1)
+        ptrs, lds = _panel_args(feats)
+        zp = torch.empty(H * n, dtype=torch.float32, device=dev)
+        zq = torch.empty(H * n, dtype=torch.float32, device=dev)
+        work = torch.empty((H * (H + 1) // 2 + H) * n, dtype=torch.float32, device=dev)
+        P = torch.empty((n, H), dtype=torch.float32, device=dev)
+        out = torch.empty((n, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.stream(dev)
+            _lib.call(dev, "srg_hop_recur_scores_f32", ptrs, lds, T, end, w.data_ptr(), zp.data_ptr(), zq.data_ptr(),
+                      n, d, st)
+            _lib.call(dev, "srg_hop_recur_attend_f32", ptrs, lds, T, end, zp.data_ptr(), zq.data_ptr(), b.data_ptr(),
+                      work.data_ptr(), P.data_ptr(), out.data_ptr(), d, n, d, st)
+        ctx.save_for_backward(zq, work, *feats)
+        ctx.meta = (end, weight.shape, bias.shape)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        zq, work, *feats = ctx.saved_tensors
+        end, w_shape, b_shape = ctx.meta
+        want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none = (None,) * (1 + len(feats))
+        if not (want_w or want_b):
+            return (None, None) + none
+        dev = feats[0].device
+        n, d = feats[0].shape
+        T, H = len(feats), end
+        G = grad if grad.dtype == torch.float32 and grad.stride(1) == 1 and (n <= 1 or grad.stride(0) >= d) \
+            else grad.to(torch.float32).contiguous()
+        ldg = G.stride(0) if n > 1 else d
+        ptrs, lds = _panel_args(feats)
+        dzp = torch.empty(H * n, dtype=torch.float32, device=dev)
+        dzq = torch.empty(H * n, dtype=torch.float32, device=dev)
+        dw = torch.empty(2 * d, dtype=torch.float32, device=dev) if want_w else None
+        db = torch.empty(1, dtype=torch.float32, device=dev) if want_b else None
+        nbytes = ctypes.c_int64(0)
+        _lib.check(_lib.query("srg_hop_recur_scores_grad_scratch_bytes", n, d, H, ctypes.byref(nbytes)),
+                   "srg_hop_recur_scores_grad_scratch_bytes")
+        with torch.cuda.device(dev):
+            st = _lib.stream(dev)
+            _lib.call(dev, "srg_hop_recur_attend_grad_f32", ptrs, lds, T, end, G.data_ptr(), ldg, zq.data_ptr(),
+                      work.data_ptr(), dzp.data_ptr(), dzq.data_ptr(), n, d, st)
+            scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+            _lib.call(dev, "srg_hop_recur_scores_grad_f32", ptrs, lds, T, end, dzp.data_ptr(), dzq.data_ptr(),
+                      dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
+                      n, d, st)
+        return (dw.view(w_shape) if want_w else None, db.view(b_shape) if want_b else None) + none
+
+
+def hop_attention_recursive(feat_list, end, weight, bias):
+    """The reference's recursive hop attention over feat_list[0 : end] (IterateLearnableWeightedMessageOp with
+    start == 0, the only start it works with; later hops are ignored): hop i's per-node weight is
+    sigmoid(Linear(2d, 1)([hop i | the combination so far])), the weights so far are re-softmaxed, and out is
+    the combination under the last weights.  Differentiable once in `weight` ([1, 2d]) and `bias` ([1]).
+    feat_list as for hop_attention.  Raises if a fused kernel cannot run."""
+    _, end = _check(feat_list, 0, end, "recursive", weight, bias, kinds=("recursive",))
+    return _HopAttentionRecursive.apply(weight, bias, end, *feat_list)
