@@ -525,6 +525,51 @@ int srg_hop_recur_scores_grad_f32(const float* const* panels, const int64_t* ldp
                                   const float* dzp, const float* dzq, float* dw, float* db, void* scratch, int64_t n,
                                   int32_t d, void* stream);
 
+/* The eight panel-reading entries above over a mini-batch of rows, without gathering the panels first
+ * (the reference's loop, models/base_scalable/base_model.py BaseSGModel.forward, gathers
+ * feat[idx] from every hop for every batch).  Each takes its base entry's arguments plus, after ldp,
+ *   rows   B int64 on the device: batch row r of panel t is panel row rows[r], at panels[t] + rows[r] * ldp[t];
+ *   n_src  the panels' row count;
+ * and n = B.  Everything that is not a panel -- zflat, zp, zq, P, dP, dz*, work, out, G, the scratch (the
+ * *_scratch_bytes queries with n = B), the SRG_HOP_PAIR_FLAT pairing zflat[i*H + h], the groups of the
+ * parameter gradient (rpg a function of B) and the order of every fma chain -- is indexed by the batch row,
+ * ascending in batch order, never in source order; duplicates and any order of indices are fine.  A result's
+ * bits are those of the base entry run on [B, d] copies of the indexed rows that have the panels' access
+ * width (16, 8 or 4 bytes): the same loads feed the same operations in the same order.  rows == NULL is the
+ * identity: the base entry itself, n_src is not looked at.
+ * Out of range: an index outside [0, n_src) is never used as an address; its batch row reads as a row of
+ * +0.0f in every panel (srg_gather_rows_f32's "no fault", with the value defined).  rows is device memory, so
+ * an entry cannot check it: wrap negative indices and validate on the caller's side where that matters.
+ * The parameter gradient loads 16 rows a step and fetches the next step's indices behind them, so the
+ * index -> address -> row chain does not serialise; the order of its fmas is the base entry's.  No atomics;
+ * asynchronous on `stream`; n == 0 as the base entries. */
+int srg_hop_scores_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                            int32_t T, int32_t start, int32_t end, int kind, const float* w, const float* b,
+                            float* zflat, int64_t n, int32_t d, void* stream);
+int srg_hop_attend_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                            int32_t T, int32_t start, int32_t end, const float* zflat, int pairing, float* P,
+                            float* out, int64_t ldo, int64_t n, int32_t d, void* stream);
+int srg_hop_attend_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                 int32_t T, int32_t start, int32_t end, const float* G, int64_t ldg,
+                                 const float* zflat, const float* P, int pairing, float* dP, float* dzflat, int64_t n,
+                                 int32_t d, void* stream);
+int srg_hop_scores_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                 int32_t T, int32_t start, int32_t end, int kind, const float* dzflat, float* dw,
+                                 float* db, void* scratch, int64_t n, int32_t d, void* stream);
+int srg_hop_recur_scores_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                  int32_t T, int32_t end, const float* w, float* zp, float* zq, int64_t n, int32_t d,
+                                  void* stream);
+int srg_hop_recur_attend_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                  int32_t T, int32_t end, const float* zp, const float* zq, const float* b,
+                                  float* work, float* P, float* out, int64_t ldo, int64_t n, int32_t d, void* stream);
+int srg_hop_recur_attend_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows,
+                                       int64_t n_src, int32_t T, int32_t end, const float* G, int64_t ldg,
+                                       const float* zq, const float* work, float* dzp, float* dzq, int64_t n,
+                                       int32_t d, void* stream);
+int srg_hop_recur_scores_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows,
+                                       int64_t n_src, int32_t T, int32_t end, const float* dzp, const float* dzq,
+                                       float* dw, float* db, void* scratch, int64_t n, int32_t d, void* stream);
+
 /* srg_spmm_csr_f32 with the aggregation step fused into its epilogue: Y = A*X as above and, for
  * every element y stored, agg = (agg_init ? 0 : agg) + w*y (separate multiply / add) -- the same
  * result as srg_spmm_csr_f32 followed by srg_hop_accumulate_f32(INIT or ADD), one panel pass less.

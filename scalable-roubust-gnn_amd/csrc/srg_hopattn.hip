@@ -3,7 +3,9 @@
 // the [H*n, (T+1)*d] panel the reference's torch composition builds: scores, attend, attend gradient and
 // the parameter gradient, each a streaming pass over the hop panels; and the recursive
 // attention of iterate_learnable_weighted_message_op.py, the same four steps around a scalar recurrence per
-// row (the srg_hop_recur_* entries).
+// row (the srg_hop_recur_* entries).  Every kernel that reads a hop panel has a row-indexed
+// form (ROWS = true, the srg_hop_*_rows_f32 entries): batch row r of panel t is panel row
+// rows[r], everything else is indexed by r.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +33,34 @@ __host__ __device__ __forceinline__ int ref_dim(int kind, int T, int d)
     return kind == SRG_HOP_JK ? T * d : kind == SRG_HOP_ORI_REF ? d : 0;
 }
 
+// The panel row behind batch row r.  ROWS = false: r itself, readable when the batch row is live.  ROWS = true:
+// rows[r], one 8-byte load per batch row that serves every panel of the row's step; an index outside
+// [0, n_src) is not readable and its row counts as +0.0f in every column (row 0's address stands in and is
+// never dereferenced).
+template <bool ROWS>
+__device__ __forceinline__ int64_t panel_row(const int64_t* __restrict__ rows, int64_t n_src, int64_t r, bool live,
+                                             bool& readable)
+{
+    if constexpr (ROWS) {
+        const int64_t src = live ? rows[r] : -1;
+        readable = (uint64_t)src < (uint64_t)n_src;
+        return readable ? src : 0;
+    } else {
+        readable = live;
+        return r;
+    }
+}
+// VEC elements of a panel row, or zeros for a row that is not readable (ROWS = false: a plain load, the
+// caller's loop runs for live rows only).
+template <int VEC, bool ROWS>
+__device__ __forceinline__ typename Vec<float, VEC>::type panel_load(const float* p, bool readable)
+{
+    if constexpr (ROWS) {
+        if (!readable) return vzero<float, VEC>();
+    }
+    return vload<float, VEC>(p);
+}
+
 // ------------------------------------------------------------------------------------------------
 // scores: zflat[h * n + i] = (ref(i) + hop(h, i)) + b   (gate: hop(h, i) + b)
 //   ref(i)    = sum over the reference panels t ascending, columns in lane order, of w[t*d + c] * F_t[i, c]
@@ -44,10 +74,11 @@ __host__ __device__ __forceinline__ int ref_dim(int kind, int T, int d)
 // d, T, the slice and VEC only.  (Loading the rows of four panels ahead of the first fold measured slower,
 // 0.49 against 0.30 ms at n = 200,000, T = 11, d = 128: 100 registers per lane instead of 30.)
 // ------------------------------------------------------------------------------------------------
-template <int VEC>
+template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_scores(HopPanels pl, int T, int start, int H, int kind, const float* __restrict__ w,
-             const float* __restrict__ b, float* __restrict__ zflat, int64_t n, int d, int cpr, int lgS)
+             const float* __restrict__ b, float* __restrict__ zflat, int64_t n, int d, int cpr, int lgS,
+             const int64_t* __restrict__ rows, int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
     const int S = 1 << lgS, R = 64 >> lgS;
@@ -61,16 +92,18 @@ k_hop_scores(HopPanels pl, int T, int start, int H, int kind, const float* __res
     for (int64_t base = wave * R; base < n; base += waves * R) {
         const int64_t r = base + g;
         const bool live = r < n;
+        bool readable;
+        const int64_t pr = panel_row<ROWS>(rows, n_src, r, live, readable);
         float ref = 0.0f;
         for (int t = 0; t < T; ++t) {
             const int h = t - start;
             const bool hop = h >= 0 && h < H, rf = is_ref(kind, t);
             if (!hop && !rf) continue;
-            const float* xr = pl.p[t] + r * pl.ld[t];
+            const float* xr = pl.p[t] + pr * pl.ld[t];
             const float* wr = w + (int64_t)t * d;
             float hp = 0.0f;
             for (int c = c0; live && c < cpr; c += S) {
-                const V xc = vload<float, VEC>(xr + (int64_t)c * VEC);
+                const V xc = panel_load<VEC, ROWS>(xr + (int64_t)c * VEC, readable);
                 if (rf) {
                     const V wc = vload<float, VEC>(wr + (int64_t)c * VEC);
 #pragma unroll
@@ -125,10 +158,10 @@ k_hop_softmax(const float* __restrict__ zflat, int flat, float* __restrict__ P, 
 }
 
 // out[i, :] = P[i, 0] * F_0[i, :] + P[i, 1] * F_1[i, :] + ... in ascending h, separate multiply and add.
-template <int VEC>
+template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_combine(HopPanels pl, int start, int H, const float* __restrict__ P, float* __restrict__ out, int64_t ldo,
-              int64_t n, int cpr, int lgS)
+              int64_t n, int cpr, int lgS, const int64_t* __restrict__ rows, int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
     const int S = 1 << lgS, R = 64 >> lgS;
@@ -139,12 +172,14 @@ k_hop_combine(HopPanels pl, int start, int H, const float* __restrict__ P, float
     for (int64_t base = wave * R; base < n; base += waves * R) {
         const int64_t r = base + g;
         if (r >= n) continue;
+        bool readable;
+        const int64_t xr = panel_row<ROWS>(rows, n_src, r, true, readable);
         const float* pr = P + r * H;
         for (int c = c0; c < cpr; c += S) {
             V acc;
 #pragma unroll 4
             for (int h = 0; h < H; ++h) {
-                const V xc = vload<float, VEC>(pl.p[start + h] + r * pl.ld[start + h] + (int64_t)c * VEC);
+                const V xc = panel_load<VEC, ROWS>(pl.p[start + h] + xr * pl.ld[start + h] + (int64_t)c * VEC, readable);
                 const float ph = pr[h];
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
@@ -159,10 +194,10 @@ k_hop_combine(HopPanels pl, int start, int H, const float* __restrict__ P, float
 
 // dP[i, h] = G[i, :] . F_{start+h}[i, :]: the scores' lane layout, one fma chain per lane from +0 in chunk
 // order, xor butterfly.  HOP_MAJOR stores dP[h * n + i] (the recursive attention's per-row vectors).
-template <int VEC, bool HOP_MAJOR = false>
+template <int VEC, bool HOP_MAJOR, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_rowdots(HopPanels pl, int start, int H, const float* __restrict__ G, int64_t ldg, float* __restrict__ dP,
-              int64_t n, int cpr, int lgS)
+              int64_t n, int cpr, int lgS, const int64_t* __restrict__ rows, int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
     const int S = 1 << lgS, R = 64 >> lgS;
@@ -173,12 +208,14 @@ k_hop_rowdots(HopPanels pl, int start, int H, const float* __restrict__ G, int64
     for (int64_t base = wave * R; base < n; base += waves * R) {
         const int64_t r = base + g;
         const bool live = r < n;
+        bool readable;
+        const int64_t pr = panel_row<ROWS>(rows, n_src, r, live, readable);
         const float* gr = G + r * ldg;
         for (int h = 0; h < H; ++h) {
-            const float* xr = pl.p[start + h] + r * pl.ld[start + h];
+            const float* xr = pl.p[start + h] + pr * pl.ld[start + h];
             float dot = 0.0f;
             for (int c = c0; live && c < cpr; c += S) {
-                const V xc = vload<float, VEC>(xr + (int64_t)c * VEC);
+                const V xc = panel_load<VEC, ROWS>(xr + (int64_t)c * VEC, readable);
                 const V gc = vload<float, VEC>(gr + (int64_t)c * VEC);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) dot = __builtin_fmaf(elem(gc, j), elem(xc, j), dot);
@@ -237,11 +274,63 @@ k_hop_dzsum(const float* __restrict__ dzflat, float* __restrict__ s, int64_t n, 
 // a panel row loaded once for both; the hop parts are added in ascending h (the first as it is) into
 // partials[q, R + c]; the group's bias part s[i0] + s[i0+1] + ... goes to partials[q, in_dim].
 // ------------------------------------------------------------------------------------------------
-template <int VEC>
+
+// The row loop of stage 1 under an index: fold(i, F[rows[i], chunk]) for i = i0 .. i1-1 ascending, ROWS_STEP
+// rows a step.  The step is 16 rows where the identity loop unrolls 4: a group is one chain per column, the
+// launch is a few waves per CU, and a row at a random address takes longer to arrive than the next row of a
+// stream, so what sets the rate is how many row loads a thread has in flight (measured in DESIGN.md §5.4.4).
+// A row's load waits for its index (index -> address -> row), so the next step's indices are fetched ahead:
+// queued right behind this step's row loads -- loads return in order, so they hold no row up -- and back
+// before the step's folds are done.  No branch stands between the loads of a step: an index that is out of
+// range loads row 0 (there is one: n_src > 0) and its value is replaced by zeros; positions past i1 repeat the
+// group's last row and are never folded.  The rows' two factors a[i], b[i] (s and dz, or dzp and dzq) are loaded
+// with the step's rows, not one pair per fold: each fold would otherwise wait out a load of its own.  x points at
+// the thread's chunk of panel row 0; fold(a[i], b[i], row).
+constexpr int ROWS_STEP = 16;
+template <int VEC, typename Fold>
+__device__ __forceinline__ void indexed_rows(const float* x, int64_t ldx, const int64_t* __restrict__ rows,
+                                             int64_t n_src, int64_t i0, int64_t i1, const float* __restrict__ a,
+                                             const float* __restrict__ b, Fold fold)
+{
+    typedef typename Vec<float, VEC>::type V;
+    if (n_src <= 0) {   // no panel row to stand in: every row reads as zeros
+        for (int64_t i = i0; i < i1; ++i) fold(a[i], b[i], vzero<float, VEC>());
+        return;
+    }
+    int64_t idx[ROWS_STEP];
+#pragma unroll
+    for (int u = 0; u < ROWS_STEP; ++u) idx[u] = rows[i0 + u < i1 ? i0 + u : i1 - 1];
+    for (int64_t i = i0; i < i1; i += ROWS_STEP) {
+        V xc[ROWS_STEP];
+        float av[ROWS_STEP], bv[ROWS_STEP];
+        bool readable[ROWS_STEP];
+#pragma unroll
+        for (int u = 0; u < ROWS_STEP; ++u) {
+            readable[u] = (uint64_t)idx[u] < (uint64_t)n_src;
+            xc[u] = vload<float, VEC>(x + (readable[u] ? idx[u] : 0) * ldx);
+        }
+#pragma unroll
+        for (int u = 0; u < ROWS_STEP; ++u) {
+            const int64_t j = i + u < i1 ? i + u : i1 - 1;
+            av[u] = a[j];
+            bv[u] = b[j];
+        }
+#pragma unroll
+        for (int u = 0; u < ROWS_STEP; ++u) {
+            const int64_t j = i + ROWS_STEP + u;
+            idx[u] = rows[j < i1 ? j : i1 - 1];
+        }
+#pragma unroll
+        for (int u = 0; u < ROWS_STEP; ++u)
+            if (i + u < i1) fold(av[u], bv[u], readable[u] ? xc[u] : vzero<float, VEC>());
+    }
+}
+
+template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_wgrad_partial(HopPanels pl, int T, int start, int H, int kind, const float* __restrict__ dzflat,
                     const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d, int cpr, int lgCT,
-                    int64_t rpg, int64_t n_groups, int want_w)
+                    int64_t rpg, int64_t n_groups, int want_w, const int64_t* __restrict__ rows, int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
     const int CT = 1 << lgCT;
@@ -268,14 +357,24 @@ k_hop_wgrad_partial(HopPanels pl, int T, int start, int H, int kind, const float
         const int64_t ldx = pl.ld[t];
         const float* dz = dzflat + (int64_t)(hop ? h : 0) * n;
         V ra = vzero<float, VEC>(), ha = vzero<float, VEC>();
-#pragma unroll 4
-        for (int64_t i = i0; i < i1; ++i) {
-            const V xc = vload<float, VEC>(x + i * ldx);
-            const float si = s[i], di = dz[i];
+        if constexpr (ROWS) {
+            indexed_rows<VEC>(x, ldx, rows, n_src, i0, i1, s, dz, [&](float si, float di, const V& xc) {
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                if (rf) elem(ra, j) = __builtin_fmaf(si, elem(xc, j), elem(ra, j));
-                if (hop) elem(ha, j) = __builtin_fmaf(di, elem(xc, j), elem(ha, j));
+                for (int j = 0; j < VEC; ++j) {
+                    if (rf) elem(ra, j) = __builtin_fmaf(si, elem(xc, j), elem(ra, j));
+                    if (hop) elem(ha, j) = __builtin_fmaf(di, elem(xc, j), elem(ha, j));
+                }
+            });
+        } else {
+#pragma unroll 4
+            for (int64_t i = i0; i < i1; ++i) {
+                const V xc = vload<float, VEC>(x + i * ldx);
+                const float si = s[i], di = dz[i];
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    if (rf) elem(ra, j) = __builtin_fmaf(si, elem(xc, j), elem(ra, j));
+                    if (hop) elem(ha, j) = __builtin_fmaf(di, elem(xc, j), elem(ha, j));
+                }
             }
         }
         if (rf) vstore<float, VEC>(out + (int64_t)t * d + (int64_t)c * VEC, ra, false);
@@ -310,10 +409,10 @@ k_hop_wgrad_fold(const float* __restrict__ partials, int64_t n_groups, int in_di
 // zp[h * n + i] = w_h . F_h[i, :], zq[h * n + i] = w_c . F_h[i, :]: k_hop_rowdots' lane layout, two fma
 // chains per lane from +0 in chunk order from one load of the panel row, one butterfly each.
 // ------------------------------------------------------------------------------------------------
-template <int VEC>
+template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_recur_scores(HopPanels pl, int H, const float* __restrict__ w, float* __restrict__ zp, float* __restrict__ zq,
-                   int64_t n, int d, int cpr, int lgS)
+                   int64_t n, int d, int cpr, int lgS, const int64_t* __restrict__ rows, int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
     const int S = 1 << lgS, R = 64 >> lgS;
@@ -325,11 +424,13 @@ k_hop_recur_scores(HopPanels pl, int H, const float* __restrict__ w, float* __re
     for (int64_t base = wave * R; base < n; base += waves * R) {
         const int64_t r = base + g;
         const bool live = r < n;
+        bool readable;
+        const int64_t pr = panel_row<ROWS>(rows, n_src, r, live, readable);
         for (int h = 0; h < H; ++h) {
-            const float* xr = pl.p[h] + r * pl.ld[h];
+            const float* xr = pl.p[h] + pr * pl.ld[h];
             float p = 0.0f, q = 0.0f;
             for (int c = c0; live && c < cpr; c += S) {
-                const V xc = vload<float, VEC>(xr + (int64_t)c * VEC);
+                const V xc = panel_load<VEC, ROWS>(xr + (int64_t)c * VEC, readable);
                 const V hc = vload<float, VEC>(w + (int64_t)c * VEC);
                 const V cc = vload<float, VEC>(wc + (int64_t)c * VEC);
 #pragma unroll
@@ -488,11 +589,12 @@ k_hop_recur_backward(const float* __restrict__ zq, const float* __restrict__ wor
 //   hp_h[c] = fma(dzp[h, i], F_h[i, c], hp_h[c])      cp_h[c] = fma(dzq[h, i], F_h[i, c], cp_h[c])
 // each kind added over h ascending (the first as it is) into partials[q, c] and partials[q, d + c]; the
 // group's bias part s[i0] + s[i0+1] + ... (s[i] = dzp[0, i] + dzp[1, i] + ...) goes to partials[q, 2d].
-template <int VEC>
+template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_recur_wgrad_partial(HopPanels pl, int H, const float* __restrict__ dzp, const float* __restrict__ dzq,
                           const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d, int cpr,
-                          int lgCT, int64_t rpg, int64_t n_groups, int want_w)
+                          int lgCT, int64_t rpg, int64_t n_groups, int want_w, const int64_t* __restrict__ rows,
+                          int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
     const int CT = 1 << lgCT;
@@ -516,14 +618,24 @@ k_hop_recur_wgrad_partial(HopPanels pl, int H, const float* __restrict__ dzp, co
         const float* dp = dzp + (int64_t)h * n;
         const float* dq = dzq + (int64_t)h * n;
         V ha = vzero<float, VEC>(), ca = vzero<float, VEC>();
-#pragma unroll 4
-        for (int64_t i = i0; i < i1; ++i) {
-            const V xc = vload<float, VEC>(x + i * ldx);
-            const float pi = dp[i], qi = dq[i];
+        if constexpr (ROWS) {
+            indexed_rows<VEC>(x, ldx, rows, n_src, i0, i1, dp, dq, [&](float pi, float qi, const V& xc) {
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
-                elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
+                for (int j = 0; j < VEC; ++j) {
+                    elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
+                    elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
+                }
+            });
+        } else {
+#pragma unroll 4
+            for (int64_t i = i0; i < i1; ++i) {
+                const V xc = vload<float, VEC>(x + i * ldx);
+                const float pi = dp[i], qi = dq[i];
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
+                    elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
+                }
             }
         }
 #pragma unroll
@@ -610,20 +722,34 @@ int check_pairing(int pairing)
     return SRG_OK;
 }
 
-#define SRG_HOP_BY_VEC(vec, LAUNCH)   \
-    do {                              \
-        if ((vec) == 4) { LAUNCH(4); } else if ((vec) == 2) { LAUNCH(2); } else { LAUNCH(1); } \
+// LAUNCH(VEC, ROWS) under the panels' access width; ROWS = true with an index, the identity kernels without
+#define SRG_HOP_BY_VEC(vec, rows, LAUNCH)   \
+    do {                                    \
+        if (rows) {                         \
+            if ((vec) == 4) { LAUNCH(4, true); } else if ((vec) == 2) { LAUNCH(2, true); } else { LAUNCH(1, true); } \
+        } else {                            \
+            if ((vec) == 4) { LAUNCH(4, false); } else if ((vec) == 2) { LAUNCH(2, false); } else { LAUNCH(1, false); } \
+        }                                   \
     } while (0)
+
+// the row index of the *_rows_* entries: NULL is the identity (n_src is not looked at)
+int check_rows(const int64_t* rows, int64_t n_src)
+{
+    if (rows && n_src < 0) return srg_fail(SRG_ERR_INVALID, "n_src=%lld panel rows", (long long)n_src);
+    return SRG_OK;
+}
 
 }  // namespace
 
 extern "C" {
 
-int srg_hop_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
-                       int kind, const float* w, const float* b, float* zflat, int64_t n, int32_t d, void* stream)
+int srg_hop_scores_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                            int32_t T, int32_t start, int32_t end, int kind, const float* w, const float* b,
+                            float* zflat, int64_t n, int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_kind(kind)) return rc;
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     const void* wide[] = {w};
     const int64_t wide_ld[] = {0};
@@ -632,20 +758,27 @@ int srg_hop_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T
     if (!b || !zflat) return srg_fail(SRG_ERR_INVALID, "null pointer");
     const int H = end - start;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_scores<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, T, start, H, kind, \
-                                     w, b, zflat, n, d, hs.cpr, hs.lgS)
-    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_scores<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, T, start, H, \
+                                        kind, w, b, zflat, n, d, hs.cpr, hs.lgS, rows, n_src)
+    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
 #undef LAUNCH
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
 
-int srg_hop_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
-                       const float* zflat, int pairing, float* P, float* out, int64_t ldo, int64_t n, int32_t d,
-                       void* stream)
+int srg_hop_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                       int kind, const float* w, const float* b, float* zflat, int64_t n, int32_t d, void* stream)
+{
+    return srg_hop_scores_rows_f32(panels, ldp, nullptr, 0, T, start, end, kind, w, b, zflat, n, d, stream);
+}
+
+int srg_hop_attend_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                            int32_t T, int32_t start, int32_t end, const float* zflat, int pairing, float* P,
+                            float* out, int64_t ldo, int64_t n, int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_pairing(pairing)) return rc;
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     const void* wide[] = {out};
     const int64_t wide_ld[] = {ldo};
@@ -658,20 +791,29 @@ int srg_hop_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T
         if (out == panels[t]) return srg_fail(SRG_ERR_INVALID, "out must not alias a hop panel");
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_hop_softmax, dim3(hs.thread_blocks), dim3(256), 0, st, zflat, pairing, P, n, H);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_combine<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, P, out, \
-                                     ldo, n, hs.cpr, hs.lgS)
-    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_combine<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, P, \
+                                        out, ldo, n, hs.cpr, hs.lgS, rows, n_src)
+    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
 #undef LAUNCH
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
 
-int srg_hop_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
-                            const float* G, int64_t ldg, const float* zflat, const float* P, int pairing,
-                            float* dP, float* dzflat, int64_t n, int32_t d, void* stream)
+int srg_hop_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                       const float* zflat, int pairing, float* P, float* out, int64_t ldo, int64_t n, int32_t d,
+                       void* stream)
+{
+    return srg_hop_attend_rows_f32(panels, ldp, nullptr, 0, T, start, end, zflat, pairing, P, out, ldo, n, d, stream);
+}
+
+int srg_hop_attend_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                 int32_t T, int32_t start, int32_t end, const float* G, int64_t ldg,
+                                 const float* zflat, const float* P, int pairing, float* dP, float* dzflat, int64_t n,
+                                 int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_pairing(pairing)) return rc;
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     const void* wide[] = {G};
     const int64_t wide_ld[] = {ldg};
@@ -682,13 +824,21 @@ int srg_hop_attend_grad_f32(const float* const* panels, const int64_t* ldp, int3
     if (dzflat == zflat || dP == P) return srg_fail(SRG_ERR_INVALID, "dzflat / dP must not alias zflat / P");
     const int H = end - start;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_rowdots<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, G, ldg, \
-                                     dP, n, hs.cpr, hs.lgS)
-    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_rowdots<V, false, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, \
+                                        H, G, ldg, dP, n, hs.cpr, hs.lgS, rows, n_src)
+    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
 #undef LAUNCH
     hipLaunchKernelGGL(k_hop_jacobian, dim3(hs.thread_blocks), dim3(256), 0, st, zflat, pairing, P, dP, dzflat, n, H);
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
+}
+
+int srg_hop_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                            const float* G, int64_t ldg, const float* zflat, const float* P, int pairing,
+                            float* dP, float* dzflat, int64_t n, int32_t d, void* stream)
+{
+    return srg_hop_attend_grad_rows_f32(panels, ldp, nullptr, 0, T, start, end, G, ldg, zflat, P, pairing, dP, dzflat,
+                                        n, d, stream);
 }
 
 int srg_hop_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t T, int32_t H, int kind, int64_t* bytes)
@@ -703,12 +853,13 @@ int srg_hop_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t T, int32_t H
     return srg_ok();
 }
 
-int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
-                            int kind, const float* dzflat, float* dw, float* db, void* scratch, int64_t n,
-                            int32_t d, void* stream)
+int srg_hop_scores_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                 int32_t T, int32_t start, int32_t end, int kind, const float* dzflat, float* dw,
+                                 float* db, void* scratch, int64_t n, int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_kind(kind)) return rc;
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     if (int rc = hop_shape(panels, ldp, T, start, end, n, d, nullptr, nullptr, 0, hs)) return rc;
     if (!dw && !db) return srg_ok();
@@ -732,9 +883,9 @@ int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int3
     const dim3 grid((unsigned)((n_groups + groups_per_block - 1) / groups_per_block),
                     (unsigned)((cpr + (1 << lgCT) - 1) >> lgCT));
     hipLaunchKernelGGL(k_hop_dzsum, dim3(hs.thread_blocks), dim3(256), 0, st, dzflat, s, n, H);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_wgrad_partial<V>), grid, dim3(256), 0, st, hs.pl, T, start, H, kind, dzflat, \
-                                     s, partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr)
-    SRG_HOP_BY_VEC(vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_wgrad_partial<V, R>), grid, dim3(256), 0, st, hs.pl, T, start, H, kind, \
+                                        dzflat, s, partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr, rows, n_src)
+    SRG_HOP_BY_VEC(vec, rows, LAUNCH);
 #undef LAUNCH
     hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials,
                        n_groups, in_dim, dw, db);
@@ -742,12 +893,22 @@ int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int3
     return srg_ok();
 }
 
+int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
+                            int kind, const float* dzflat, float* dw, float* db, void* scratch, int64_t n,
+                            int32_t d, void* stream)
+{
+    return srg_hop_scores_grad_rows_f32(panels, ldp, nullptr, 0, T, start, end, kind, dzflat, dw, db, scratch, n, d,
+                                        stream);
+}
+
 // ---- the recursive attention (start == 0: the reference works with no other) ----
 
-int srg_hop_recur_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* w,
-                             float* zp, float* zq, int64_t n, int32_t d, void* stream)
+int srg_hop_recur_scores_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                  int32_t T, int32_t end, const float* w, float* zp, float* zq, int64_t n, int32_t d,
+                                  void* stream)
 {
     SRG_DEVICE_GUARD(stream);
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     const void* wide[] = {w};
     const int64_t wide_ld[] = {0};
@@ -755,19 +916,26 @@ int srg_hop_recur_scores_f32(const float* const* panels, const int64_t* ldp, int
     if (n == 0) return srg_ok();
     if (!zp || !zq || zp == zq) return srg_fail(SRG_ERR_INVALID, "zp / zq null or the same");
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_recur_scores<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, end, w, zp, \
-                                     zq, n, d, hs.cpr, hs.lgS)
-    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_recur_scores<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, end, w, \
+                                        zp, zq, n, d, hs.cpr, hs.lgS, rows, n_src)
+    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
 #undef LAUNCH
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
 
-int srg_hop_recur_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* zp,
-                             const float* zq, const float* b, float* work, float* P, float* out, int64_t ldo,
-                             int64_t n, int32_t d, void* stream)
+int srg_hop_recur_scores_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* w,
+                             float* zp, float* zq, int64_t n, int32_t d, void* stream)
+{
+    return srg_hop_recur_scores_rows_f32(panels, ldp, nullptr, 0, T, end, w, zp, zq, n, d, stream);
+}
+
+int srg_hop_recur_attend_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows, int64_t n_src,
+                                  int32_t T, int32_t end, const float* zp, const float* zq, const float* b,
+                                  float* work, float* P, float* out, int64_t ldo, int64_t n, int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     const void* wide[] = {out};
     const int64_t wide_ld[] = {ldo};
@@ -780,19 +948,28 @@ int srg_hop_recur_attend_f32(const float* const* panels, const int64_t* ldp, int
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_hop_recur_forward, dim3(recur_blocks(n)), dim3(RECUR_BLOCK),
                        (size_t)RECUR_FWD_VECTORS * end * RECUR_BLOCK * sizeof(float), st, zp, zq, b, work, P, n, end);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_combine<V>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, P, out, \
-                                     ldo, n, hs.cpr, hs.lgS)
-    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_combine<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, P, \
+                                        out, ldo, n, hs.cpr, hs.lgS, rows, n_src)
+    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
 #undef LAUNCH
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
 
-int srg_hop_recur_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
-                                  const float* G, int64_t ldg, const float* zq, const float* work, float* dzp,
-                                  float* dzq, int64_t n, int32_t d, void* stream)
+int srg_hop_recur_attend_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end, const float* zp,
+                             const float* zq, const float* b, float* work, float* P, float* out, int64_t ldo,
+                             int64_t n, int32_t d, void* stream)
+{
+    return srg_hop_recur_attend_rows_f32(panels, ldp, nullptr, 0, T, end, zp, zq, b, work, P, out, ldo, n, d, stream);
+}
+
+int srg_hop_recur_attend_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows,
+                                       int64_t n_src, int32_t T, int32_t end, const float* G, int64_t ldg,
+                                       const float* zq, const float* work, float* dzp, float* dzq, int64_t n,
+                                       int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     const void* wide[] = {G};
     const int64_t wide_ld[] = {ldg};
@@ -802,14 +979,21 @@ int srg_hop_recur_attend_grad_f32(const float* const* panels, const int64_t* ldp
     if (!zq || !work || !dzp || !dzq) return srg_fail(SRG_ERR_INVALID, "null pointer");
     if (dzp == dzq || dzp == zq || dzq == zq) return srg_fail(SRG_ERR_INVALID, "dzp, dzq and zq must not alias");
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_rowdots<V, true>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, G, \
-                                     ldg, dzp, n, hs.cpr, hs.lgS)
-    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_rowdots<V, true, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, \
+                                        G, ldg, dzp, n, hs.cpr, hs.lgS, rows, n_src)
+    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
 #undef LAUNCH
     hipLaunchKernelGGL(k_hop_recur_backward, dim3(recur_blocks(n)), dim3(RECUR_BLOCK),
                        (size_t)RECUR_BWD_VECTORS * end * RECUR_BLOCK * sizeof(float), st, zq, work, dzp, dzq, n, end);
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
+}
+
+int srg_hop_recur_attend_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
+                                  const float* G, int64_t ldg, const float* zq, const float* work, float* dzp,
+                                  float* dzq, int64_t n, int32_t d, void* stream)
+{
+    return srg_hop_recur_attend_grad_rows_f32(panels, ldp, nullptr, 0, T, end, G, ldg, zq, work, dzp, dzq, n, d, stream);
 }
 
 int srg_hop_recur_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t H, int64_t* bytes)
@@ -823,11 +1007,12 @@ int srg_hop_recur_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t H, int
     return srg_ok();
 }
 
-int srg_hop_recur_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
-                                  const float* dzp, const float* dzq, float* dw, float* db, void* scratch, int64_t n,
-                                  int32_t d, void* stream)
+int srg_hop_recur_scores_grad_rows_f32(const float* const* panels, const int64_t* ldp, const int64_t* rows,
+                                       int64_t n_src, int32_t T, int32_t end, const float* dzp, const float* dzq,
+                                       float* dw, float* db, void* scratch, int64_t n, int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
+    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
     if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, nullptr, nullptr, 0, hs)) return rc;
     if (!dw && !db) return srg_ok();
@@ -850,14 +1035,21 @@ int srg_hop_recur_scores_grad_f32(const float* const* panels, const int64_t* ldp
     const dim3 grid((unsigned)((n_groups + groups_per_block - 1) / groups_per_block),
                     (unsigned)((cpr + (1 << lgCT) - 1) >> lgCT));
     hipLaunchKernelGGL(k_hop_dzsum, dim3(hs.thread_blocks), dim3(256), 0, st, dzp, s, n, end);
-#define LAUNCH(V) hipLaunchKernelGGL((k_hop_recur_wgrad_partial<V>), grid, dim3(256), 0, st, hs.pl, end, dzp, dzq, s, \
-                                     partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr)
-    SRG_HOP_BY_VEC(hs.vec, LAUNCH);
+#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_recur_wgrad_partial<V, R>), grid, dim3(256), 0, st, hs.pl, end, dzp, dzq, s, \
+                                        partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr, rows, n_src)
+    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
 #undef LAUNCH
     hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials,
                        n_groups, in_dim, dw, db);
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
+}
+
+int srg_hop_recur_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,
+                                  const float* dzp, const float* dzq, float* dw, float* db, void* scratch, int64_t n,
+                                  int32_t d, void* stream)
+{
+    return srg_hop_recur_scores_grad_rows_f32(panels, ldp, nullptr, 0, T, end, dzp, dzq, dw, db, scratch, n, d, stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,9 @@ requires grad, run srgnn.hop_attention.hop_attention_recursive (the device kerne
 weights within a derived rounding bound, gradients for the Linear's weight and bias, two streaming passes and a
 scalar recurrence per row instead of (end - start)^2 panel-sized steps).  Everything else takes the composition
 below, unchanged -- the IndexError the reference raises for start >= 1 included.
+
+aggregate_rows(feat_list, idx) is the mini-batch step of the reference's training loop, aggregate over
+[f[idx] for f in feat_list]; under `fused` it reads the batch's rows from the device panels in place.
 """
 import torch
 import torch.nn.functional as F
@@ -46,3 +49,28 @@ class IterateLearnableWeightedMessageOp(MessageOp):
             for j in range(1, i + 1):
                 combined = combined + torch.mul(feat_list[self.start + j], weights[:, j].view(-1, 1))
         return combined
+
+    def aggregate_rows(self, feat_list, idx):
+        """aggregate([f[idx] for f in feat_list]), the reference's mini-batch step (BaseSGModel.forward), with
+        aggregate's type checks.  With `fused` set, start == 0, float32 2-d hop tensors held on a HIP device, none
+        requiring grad, and idx a 1-d integer tensor, the kernels read the rows idx names from the panels
+        themselves (srgnn.hop_attention.hop_attention_recursive(..., index=idx)): no
+        [len(idx), d] copy per hop.  Everything else is exactly the two reference lines."""
+        if not isinstance(feat_list, list):
+            return TypeError("The input must be a list consists of feature matrices!")
+        for feat in feat_list:
+            if not isinstance(feat, torch.Tensor):
+                raise TypeError("The feature matrices must be tensors!")
+        if (self.fused and self.start == 0 and len(feat_list) > 0 and _is_row_index(idx)
+                and all(f.is_cuda and f.dim() == 2 and f.dtype == torch.float32 and not f.requires_grad
+                        for f in feat_list)):
+            from srgnn.hop_attention import hop_attention_recursive
+            return hop_attention_recursive(feat_list, self.end, self.learnable_weight.weight,
+                                           self.learnable_weight.bias, index=idx)
+        return self.aggregate([f[idx] for f in feat_list])
+
+
+def _is_row_index(idx):
+    """A 1-d integer tensor: the index the device path takes (a mask or a slice selects rows another way)."""
+    return (isinstance(idx, torch.Tensor) and idx.dim() == 1 and idx.dtype != torch.bool
+            and not idx.dtype.is_floating_point and not idx.dtype.is_complex)

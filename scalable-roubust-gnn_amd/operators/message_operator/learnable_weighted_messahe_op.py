@@ -12,6 +12,9 @@ the same initial values), same forward arithmetic.
 which requires grad, run srgnn.hop_attention (the device kernels of DESIGN.md §5.4.2: the same weights
 within a derived rounding bound, gradients for the Linear's weight and bias, none of the composition's
 [hops * n, in_dim] temporaries).  Everything else takes the composition below, unchanged.
+
+aggregate_rows(feat_list, idx) is the mini-batch step of the reference's training loop, aggregate over
+[f[idx] for f in feat_list]; under `fused` it reads the batch's rows from the device panels in place.
 """
 import torch
 import torch.nn.functional as F
@@ -72,3 +75,27 @@ class LearnableWeightedMessageOp(MessageOp):
         weights = self._hop_weights(feat_list)
         add = one_dim_weighted_add if self.combination_type in ("simple", "simple_allow_neg") else two_dim_weighted_add
         return add(feat_list[self.start:self.end], weight_list=weights)
+
+    def aggregate_rows(self, feat_list, idx):
+        """aggregate([f[idx] for f in feat_list]), the reference's mini-batch step (BaseSGModel.forward), with
+        aggregate's type checks.  With `fused` set, gate / ori_ref / jk over 2-d hop tensors held on a HIP
+        device, none requiring grad, and idx a 1-d integer tensor, the kernels read the rows idx names from the
+        panels themselves (srgnn.hop_attention(..., index=idx)): no [len(idx), d] copy per hop.
+        Everything else is exactly the two reference lines."""
+        if not isinstance(feat_list, list):
+            return TypeError("The input must be a list consists of feature matrices!")
+        for feat in feat_list:
+            if not isinstance(feat, torch.Tensor):
+                raise TypeError("The feature matrices must be tensors!")
+        if (self.fused and self.combination_type in ("gate", "ori_ref", "jk") and _is_row_index(idx)
+                and len(feat_list) > 0 and all(f.is_cuda and f.dim() == 2 and not f.requires_grad for f in feat_list)):
+            from srgnn.hop_attention import hop_attention
+            return hop_attention(feat_list, self.start, self.end, self.combination_type,
+                                 self.learnable_weight.weight, self.learnable_weight.bias, index=idx)
+        return self.aggregate([f[idx] for f in feat_list])
+
+
+def _is_row_index(idx):
+    """A 1-d integer tensor: the index the device path takes (a mask or a slice selects rows another way)."""
+    return (isinstance(idx, torch.Tensor) and idx.dim() == 1 and idx.dtype != torch.bool
+            and not idx.dtype.is_floating_point and not idx.dtype.is_complex)

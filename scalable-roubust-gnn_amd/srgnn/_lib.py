@@ -113,6 +113,14 @@ EXPORTED_SYMBOLS = (
     "srg_hop_recur_attend_grad_f32",
     "srg_hop_recur_scores_grad_scratch_bytes",
     "srg_hop_recur_scores_grad_f32",
+    "srg_hop_scores_rows_f32",
+    "srg_hop_attend_rows_f32",
+    "srg_hop_attend_grad_rows_f32",
+    "srg_hop_scores_grad_rows_f32",
+    "srg_hop_recur_scores_rows_f32",
+    "srg_hop_recur_attend_rows_f32",
+    "srg_hop_recur_attend_grad_rows_f32",
+    "srg_hop_recur_scores_grad_rows_f32",
     "srg_spmm_agg_f32",
     "srg_spmm_span_f32",
     "srg_spmm_cheby_f32",
@@ -244,6 +252,14 @@ def _declare(lib):
                  "srg_hop_recur_scores_f32", "srg_hop_recur_attend_f32", "srg_hop_recur_attend_grad_f32",
                  "srg_hop_recur_scores_grad_scratch_bytes", "srg_hop_recur_scores_grad_f32"):
         getattr(lib, name).restype = ctypes.c_int
+    # the row-indexed twins: the base entry's arguments with (rows, n_src) after ldp
+    for name in ("srg_hop_scores_f32", "srg_hop_attend_f32", "srg_hop_attend_grad_f32", "srg_hop_scores_grad_f32",
+                 "srg_hop_recur_scores_f32", "srg_hop_recur_attend_f32", "srg_hop_recur_attend_grad_f32",
+                 "srg_hop_recur_scores_grad_f32"):
+        twin = getattr(lib, name.replace("_f32", "_rows_f32"))
+        base = getattr(lib, name).argtypes
+        twin.argtypes = list(base[:2]) + [_p, _i64] + list(base[2:])
+        twin.restype = ctypes.c_int
     lib.srg_tail_record_f32.argtypes = [_p, _p, _i64, _i32, _i64, _i32, _f32, _p]
     lib.srg_tail_record_f32.restype = ctypes.c_int
     lib.srg_tail_rowsum_f32.argtypes = [_p, _i64, _i32, _i64, _i32, _p, _i32, _p]

@@ -5,7 +5,9 @@ srg_hop_scores_grad_f32 backward, without the [H*n, (T+1)*d] panel of the torch 
 recursive): srg_hop_recur_scores_f32 + srg_hop_recur_attend_f32 forward, srg_hop_recur_attend_grad_f32 +
 srg_hop_recur_scores_grad_f32 backward, a scalar recurrence per row between two streaming passes instead of
 the composition's H^2 panel-sized steps.  The hop panels are precomputed constants:
-gradients go to the weight and the bias.
+gradients go to the weight and the bias.  With `index=` both attend over a mini-batch of rows of the panels
+through the srg_hop_*_rows_f32 entries, which read row index[r] where the others read row r: no gathered
+[B, d] copies of the hops.
 """
 from __future__ import annotations
 
@@ -34,6 +36,34 @@ def _panel_args(feats):
     ptrs = (ctypes.c_void_p * T)(*[f.data_ptr() for f in feats])
     lds = (ctypes.c_int64 * T)(*[f.stride(0) if f.shape[0] > 1 else f.shape[1] for f in feats])
     return ptrs, lds
+
+
+def _call(dev, name, ptrs, lds, index, n_src, *rest):
+    """The entry `name` on whole panels (index None), or its row-indexed twin on the rows `index` names."""
+    if index is None:
+        _lib.call(dev, name, ptrs, lds, *rest)
+    else:
+        _lib.call(dev, name.replace("_f32", "_rows_f32"), ptrs, lds, index.data_ptr(), n_src, *rest)
+
+
+def _index(index, feat_list, check):
+    """The batch rows as a contiguous int64 tensor on the panels' device.  check: one aminmax and its host sync;
+    an index outside [-n, n) raises IndexError, negative ones are wrapped as torch wraps them.  Without it the
+    index goes to the kernels as it is, where an index outside [0, n) reads as a row of zeros."""
+    if index is None:
+        return None
+    index = torch.as_tensor(index)
+    if index.dim() != 1 or index.dtype.is_floating_point or index.dtype.is_complex or index.dtype == torch.bool:
+        raise TypeError(f"hop_attention: index must be a 1-d integer tensor, got {index.dtype} {tuple(index.shape)}")
+    n = feat_list[0].shape[0]
+    index = index.to(device=feat_list[0].device, dtype=torch.int64).contiguous()
+    if check and index.numel() > 0:
+        lo, hi = (int(v) for v in torch.aminmax(index))
+        if lo < -n or hi >= n:
+            raise IndexError(f"hop_attention: index {lo if lo < -n else hi} is out of bounds for hops of {n} rows")
+        if lo < 0:
+            index = torch.where(index < 0, index + n, index)
+    return index
 
 
 def _check(feat_list, start, end, kind, weight, bias, kinds=KINDS):
@@ -78,9 +108,10 @@ def _check(feat_list, start, end, kind, weight, bias, kinds=KINDS):
 
 class _HopAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, weight, bias, start, end, kind, *feats):
+    def forward(ctx, weight, bias, start, end, kind, index, *feats):
         dev = feats[0].device
-        n, d = feats[0].shape
+        n_src, d = feats[0].shape
+        n = n_src if index is None else index.numel()
         T, H = len(feats), end - start
         w = weight.detach().contiguous().view(-1)
         b = bias.detach().contiguous().view(-1)
@@ -90,25 +121,26 @@ class _HopAttention(torch.autograd.Function):
         out = torch.empty((n, d), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = _lib.stream(dev)
-            _lib.call(dev, "srg_hop_scores_f32", ptrs, lds, T, start, end, KINDS[kind], w.data_ptr(), b.data_ptr(),
-                      zflat.data_ptr(), n, d, st)
-            _lib.call(dev, "srg_hop_attend_f32", ptrs, lds, T, start, end, zflat.data_ptr(), _pairing(kind),
-                      P.data_ptr(), out.data_ptr(), d, n, d, st)
-        ctx.save_for_backward(P, zflat, *feats)
+            _call(dev, "srg_hop_scores_f32", ptrs, lds, index, n_src, T, start, end, KINDS[kind], w.data_ptr(),
+                  b.data_ptr(), zflat.data_ptr(), n, d, st)
+            _call(dev, "srg_hop_attend_f32", ptrs, lds, index, n_src, T, start, end, zflat.data_ptr(), _pairing(kind),
+                  P.data_ptr(), out.data_ptr(), d, n, d, st)
+        ctx.save_for_backward(P, zflat, index, *feats)     # the panels by reference: no copy
         ctx.meta = (start, end, kind, weight.shape, bias.shape)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
-        P, zflat, *feats = ctx.saved_tensors
+        P, zflat, index, *feats = ctx.saved_tensors
         start, end, kind, w_shape, b_shape = ctx.meta
         want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        none = (None,) * (3 + len(feats))
+        none = (None,) * (4 + len(feats))
         if not (want_w or want_b):
             return (None, None) + none
         dev = feats[0].device
-        n, d = feats[0].shape
+        n_src, d = feats[0].shape
+        n = n_src if index is None else index.numel()
         T, H = len(feats), end - start
         G = grad if grad.dtype == torch.float32 and grad.stride(1) == 1 and (n <= 1 or grad.stride(0) >= d) \
             else grad.to(torch.float32).contiguous()
@@ -123,30 +155,39 @@ class _HopAttention(torch.autograd.Function):
                    "srg_hop_scores_grad_scratch_bytes")
         with torch.cuda.device(dev):
             st = _lib.stream(dev)
-            _lib.call(dev, "srg_hop_attend_grad_f32", ptrs, lds, T, start, end, G.data_ptr(), ldg, zflat.data_ptr(),
-                      P.data_ptr(), _pairing(kind), dP.data_ptr(), dz.data_ptr(), n, d, st)
+            _call(dev, "srg_hop_attend_grad_f32", ptrs, lds, index, n_src, T, start, end, G.data_ptr(), ldg,
+                  zflat.data_ptr(), P.data_ptr(), _pairing(kind), dP.data_ptr(), dz.data_ptr(), n, d, st)
             del dP
             scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
-            _lib.call(dev, "srg_hop_scores_grad_f32", ptrs, lds, T, start, end, KINDS[kind], dz.data_ptr(),
-                      dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
-                      n, d, st)
+            _call(dev, "srg_hop_scores_grad_f32", ptrs, lds, index, n_src, T, start, end, KINDS[kind], dz.data_ptr(),
+                  dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
+                  n, d, st)
         return (dw.view(w_shape) if want_w else None, db.view(b_shape) if want_b else None) + none
 
 
-def hop_attention(feat_list, start, end, kind, weight, bias):
+def hop_attention(feat_list, start, end, kind, weight, bias, index=None, check=True):
     """out[i] = sum_h P[i, h] * feat_list[start + h][i] with P the reference's softmax(sigmoid(scores))
     (LearnableWeightedMessageOp's gate / ori_ref / jk), differentiable once in `weight` ([1, in_dim]) and
     `bias` ([1]).  feat_list: float32 [n, d] tensors on one HIP device, none requiring grad (row strides
-    are free: column windows of wider panels pass as they are).  Raises if a fused kernel cannot run."""
+    are free: column windows of wider panels pass as they are).  Raises if a fused kernel cannot run.
+
+    index (a 1-d integer tensor of B batch rows, any order, duplicates allowed): the attention over the rows
+    feat[index] of every hop, out [B, d], with the bits of hop_attention([f[index] for f in feat_list], ...)
+    on contiguous copies of the same alignment, without making the copies; it gets no gradient.  check=True
+    validates it with one aminmax and its host sync: outside [-n, n) raises IndexError before any launch,
+    negative indices wrap as in torch.  check=False skips that (a loader whose indices were validated once):
+    an index outside [0, n) then reads as a row of zeros."""
     start, end = _check(feat_list, start, end, kind, weight, bias)
-    return _HopAttention.apply(weight, bias, start, end, kind, *feat_list)
+    index = _index(index, feat_list, check)
+    return _HopAttention.apply(weight, bias, start, end, kind, index, *feat_list)
 
 
 class _HopAttentionRecursive(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, weight, bias, end, *feats):
+    def forward(ctx, weight, bias, end, index, *feats):
         dev = feats[0].device
-        n, d = feats[0].shape
+        n_src, d = feats[0].shape
+        n = n_src if index is None else index.numel()
         T, H = len(feats), end
         w = weight.detach().contiguous().view(-1)
         b = bias.detach().contiguous().view(-1)
@@ -158,25 +199,26 @@ class _HopAttentionRecursive(torch.autograd.Function):
         out = torch.empty((n, d), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = _lib.stream(dev)
-            _lib.call(dev, "srg_hop_recur_scores_f32", ptrs, lds, T, end, w.data_ptr(), zp.data_ptr(), zq.data_ptr(),
-                      n, d, st)
-            _lib.call(dev, "srg_hop_recur_attend_f32", ptrs, lds, T, end, zp.data_ptr(), zq.data_ptr(), b.data_ptr(),
-                      work.data_ptr(), P.data_ptr(), out.data_ptr(), d, n, d, st)
-        ctx.save_for_backward(zq, work, *feats)
+            _call(dev, "srg_hop_recur_scores_f32", ptrs, lds, index, n_src, T, end, w.data_ptr(), zp.data_ptr(),
+                  zq.data_ptr(), n, d, st)
+            _call(dev, "srg_hop_recur_attend_f32", ptrs, lds, index, n_src, T, end, zp.data_ptr(), zq.data_ptr(),
+                  b.data_ptr(), work.data_ptr(), P.data_ptr(), out.data_ptr(), d, n, d, st)
+        ctx.save_for_backward(zq, work, index, *feats)     # the panels by reference: no copy
         ctx.meta = (end, weight.shape, bias.shape)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad):
-        zq, work, *feats = ctx.saved_tensors
+        zq, work, index, *feats = ctx.saved_tensors
         end, w_shape, b_shape = ctx.meta
         want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        none = (None,) * (1 + len(feats))
+        none = (None,) * (2 + len(feats))
         if not (want_w or want_b):
             return (None, None) + none
         dev = feats[0].device
-        n, d = feats[0].shape
+        n_src, d = feats[0].shape
+        n = n_src if index is None else index.numel()
         T, H = len(feats), end
         G = grad if grad.dtype == torch.float32 and grad.stride(1) == 1 and (n <= 1 or grad.stride(0) >= d) \
             else grad.to(torch.float32).contiguous()
@@ -191,20 +233,21 @@ class _HopAttentionRecursive(torch.autograd.Function):
                    "srg_hop_recur_scores_grad_scratch_bytes")
         with torch.cuda.device(dev):
             st = _lib.stream(dev)
-            _lib.call(dev, "srg_hop_recur_attend_grad_f32", ptrs, lds, T, end, G.data_ptr(), ldg, zq.data_ptr(),
-                      work.data_ptr(), dzp.data_ptr(), dzq.data_ptr(), n, d, st)
+            _call(dev, "srg_hop_recur_attend_grad_f32", ptrs, lds, index, n_src, T, end, G.data_ptr(), ldg,
+                  zq.data_ptr(), work.data_ptr(), dzp.data_ptr(), dzq.data_ptr(), n, d, st)
             scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
-            _lib.call(dev, "srg_hop_recur_scores_grad_f32", ptrs, lds, T, end, dzp.data_ptr(), dzq.data_ptr(),
-                      dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
-                      n, d, st)
+            _call(dev, "srg_hop_recur_scores_grad_f32", ptrs, lds, index, n_src, T, end, dzp.data_ptr(), dzq.data_ptr(),
+                  dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
+                  n, d, st)
         return (dw.view(w_shape) if want_w else None, db.view(b_shape) if want_b else None) + none
 
 
-def hop_attention_recursive(feat_list, end, weight, bias):
+def hop_attention_recursive(feat_list, end, weight, bias, index=None, check=True):
     """The reference's recursive hop attention over feat_list[0 : end] (IterateLearnableWeightedMessageOp with
     start == 0, the only start it works with; later hops are ignored): hop i's per-node weight is
     sigmoid(Linear(2d, 1)([hop i | the combination so far])), the weights so far are re-softmaxed, and out is
     the combination under the last weights.  Differentiable once in `weight` ([1, 2d]) and `bias` ([1]).
-    feat_list as for hop_attention.  Raises if a fused kernel cannot run."""
+    feat_list, index and check as for hop_attention.  Raises if a fused kernel cannot run."""
     _, end = _check(feat_list, 0, end, "recursive", weight, bias, kinds=("recursive",))
-    return _HopAttentionRecursive.apply(weight, bias, end, *feat_list)
+    index = _index(index, feat_list, check)
+    return _HopAttentionRecursive.apply(weight, bias, end, index, *feat_list)
