@@ -768,6 +768,30 @@ int srg_spmm_muladd_f32(const int64_t* indptr, const int32_t* indices, const flo
 int srg_sddmm_f32(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const float* G,
                   int64_t ldg, const float* X, int64_t ldx, int32_t d, const int64_t* perm, float* out,
                   void* stream);
+/* The two products of the fused graph-wavelet filter Y = phi * (theta (.) (phi^-1 * Z)) and of its adjoints
+ * (srgnn.wavelet_conv), for narrow panels (d of 1 to 64; any d works).  CSR as for
+ * srg_spmm_muladd_f32 (indptr: int64 [n_rows + 1] from 0 to nnz, trusted; a row holds fewer than 2^31
+ * entries), X [., d] with row stride ldx and Y [n_rows, d] with row stride ldy, strides in elements and
+ * >= d (column windows and unaligned bases are fine):
+ *   Y[r, j] = chain over row r's entries e in stored order of fl( fl(v_e * scale[s_e]) * X[indices[e], j] ),
+ *   s_e = r when scale_axis == 1, indices[e] when scale_axis == 0;
+ * every chain starts from +0, every product is rounded before it is added, one output is one sequential
+ * chain.  scale == NULL skips the rescale: the bits of srg_spmm_muladd_f32.  scale_axis must be 0 or 1
+ * whether or not scale is given.  NaN, +-Inf, -0 and subnormals follow IEEE through the chain.  No
+ * atomics: run-to-run identical.  n_rows == 0 or d == 0 is a no-op.  Asynchronous on `stream`. */
+int srg_spmm_scaled_f32(const int64_t* indptr, const int32_t* indices, const float* values, const float* scale,
+                        int32_t scale_axis, int64_t n_rows, const float* X, int64_t ldx, float* Y, int64_t ldy,
+                        int32_t d, void* stream);
+/* The row sums of a value-weighted sampled dense-dense product (the filter's gradient with respect to
+ * theta): for every row k of the CSR, with G [., d] (row stride ldg; rows the column ids index) and
+ * P [n_rows, d] (row stride ldp),
+ *   out[k] = chain over row k's entries e in stored order of fl( v_e * s_e ),
+ *   s_e    = chain over j ascending of fl( G[indices[e], j] * P[k, j] )   (srg_sddmm_f32's chain),
+ * from +0, products rounded before they are added.  An empty row writes +0; d == 0 writes +0 to every
+ * row.  IEEE special values pass through; no atomics.  n_rows == 0 is a no-op.  Asynchronous on `stream`. */
+int srg_sddmm_rowsum_f32(const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows,
+                         const float* G, int64_t ldg, const float* P, int64_t ldp, int32_t d, float* out,
+                         void* stream);
 
 /* ---- multi-GPU: communicators and the row-partitioned K-hop propagation ---------------------------
  * SURVEY.md §8(b) item 5, for C / C++ hosts (the Python package drives the same kernels through

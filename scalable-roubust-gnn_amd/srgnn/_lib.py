@@ -136,6 +136,8 @@ EXPORTED_SYMBOLS = (
     "srg_spgemm_grad_f32",
     "srg_spmm_muladd_f32",
     "srg_sddmm_f32",
+    "srg_spmm_scaled_f32",
+    "srg_sddmm_rowsum_f32",
     "srg_hub_join",
     "srg_hub_side_streams",
     "srg_csr_col_splits",
@@ -285,6 +287,10 @@ def _declare(lib):
     lib.srg_spmm_muladd_f32.restype = ctypes.c_int
     lib.srg_sddmm_f32.argtypes = [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _p, _p]
     lib.srg_sddmm_f32.restype = ctypes.c_int
+    lib.srg_spmm_scaled_f32.argtypes = [_p, _p, _p, _p, _i32, _i64, _p, _i64, _p, _i64, _i32, _p]
+    lib.srg_spmm_scaled_f32.restype = ctypes.c_int
+    lib.srg_sddmm_rowsum_f32.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p, _p]
+    lib.srg_sddmm_rowsum_f32.restype = ctypes.c_int
     lib.srg_hub_join.argtypes = [_p]
     lib.srg_hub_join.restype = ctypes.c_int
     lib.srg_hub_side_streams.argtypes = []
