@@ -483,7 +483,8 @@ int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int3
  * (DESIGN.md §5.4.3).  panels / ldp / T as above; the hops used are panels 0 .. end-1 (H = end, 1 <= end <= T:
  * the reference works with start == 0 only); w = [w_h | w_c] is the weight row of Linear(2d, 1) (w_h meets
  * the hop, w_c the running combination), b its bias.  With p_j = w_h . F_j[i, :] and q_j = w_c . F_j[i, :], per
- * row i:  W(0) = [1];  for k = 1 .. H-1:  r = sum_{j<k} W(k-1)_j q_j,  s = (p_k + r) + b,  g_k = 1 / (1 + expf(-s)),
+ * row i:  W(0) = [1] (NaN where (p_0 + q_0) + b is NaN: the reference's one-column softmax of a NaN gate);
+ * for k = 1 .. H-1:  r = sum_{j<k} W(k-1)_j q_j,  s = (p_k + r) + b,  g_k = 1 / (1 + expf(-s)),
  * W(k) = softmax([W(k-1)_0 .. W(k-1)_{k-1}, g_k]) (the reference re-softmaxes weights that were softmaxed
  * already; kept);  out[i, :] = sum_j W(H-1)_j F_j[i, :].  Asynchronous on `stream`, deterministic (no atomics;
  * the bits depend on the shapes and the panels' alignment only), within the bound of DESIGN.md §5.4.3 of the

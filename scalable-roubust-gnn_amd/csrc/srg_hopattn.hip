@@ -478,7 +478,7 @@ __device__ __forceinline__ void recur_fetch(float* dst, const float* __restrict_
     }
 }
 
-// One thread per row.  W(0) = [1]; for i = 1 .. H-1, with W = W(i-1):
+// One thread per row.  W(0) = [1] (NaN where s_0 = (p_0 + q_0) + b is NaN); for i = 1 .. H-1, with W = W(i-1):
 //   r = W_0 q_0 + W_1 q_1 + ... + W_{i-1} q_{i-1}   (left to right)       s = (p_i + r) + b
 //   g_i = 1 / (1 + expf(-s))
 //   e_j = expf(W_j) (j < i), e_i = expf(g_i),  W(i)_j = e_j / (e_0 + e_1 + ... + e_i)   (left to right)
@@ -499,9 +499,14 @@ k_hop_recur_forward(const float* __restrict__ zp, const float* __restrict__ zq, 
         float* gs = wr + (tri(H - 1) + H) * n;
         recur_fetch(sp, zp + r, n, H);
         recur_fetch(sq, zq + r, n, H);
-        sw[0] = 1.0f;
-        wr[0] = 1.0f;
-        gs[0] = 0.0f;   // g_0 never matters: a one-column softmax is 1
+        // W(0) = softmax([g_0]) is 1 whatever g_0 is -- except NaN: the reference's one-column softmax of a NaN
+        // gate is NaN, so a row whose score s_0 = (p_0 + q_0) + b is NaN (a NaN cell of hop 0, or Inf cells
+        // that meet with opposite signs) is NaN throughout, as there
+        const float s0 = __fadd_rn(__fadd_rn(sp[0], sq[0]), bias);
+        const float w0 = s0 != s0 ? s0 : 1.0f;
+        sw[0] = w0;
+        wr[0] = w0;
+        gs[0] = 0.0f;   // g_0 itself is never read
         for (int i = 1; i < H; ++i) {
             float* cur = wr + tri(i) * n;
             float rs = 0.0f, sum = 0.0f;

@@ -7,10 +7,26 @@ tests/test_hop_attention_{cpu,gpu}.py.  The derivation is DESIGN.md §5.4.2; in 
   an input's error goes through a differentiable step multiplied by the step's derivative.
 
 Nothing here is fitted to a result: every constant counts operations of the formula.
+
+Special values ("Special values and saturation").  A bound is finite wherever its value is
+finite.  The only place a zero factor meets an infinite bound is the sigmoid at S = +-inf (an Inf cell in a
+panel the score reads): both precisions give a = 1 / (1 + exp(-S)) = 1 or 0 EXACTLY there (exp gives 0 or +inf,
+1 + 0 = 1, 1 / inf = 0), so a carries no error of the score and a (1 - a) (E_S + 2 eps) is 0, not 0 * inf = NaN;
+the same holds for the Jacobian j = a (1 - a) = 0 times an infinite bound of its other factor.  _zmul is that
+product.  classes / check_special compare results that hold NaN or +-Inf on purpose: the class of every
+element (finite, NaN, +Inf, -Inf) must be the restatement's, and the finite ones lie within their bound.
+
+Underflow.  eps-relative error holds for an fp32 operation whose exact result is at least 2^-126 in magnitude;
+below that the result is rounded to a multiple of 2^-149, an ABSOLUTE error of at most 2^-150.  out is H
+products (the adds of subnormal terms are exact), so a row of subnormal panel cells adds at most
+underflow_allowance(H) = H * 2^-150 to E_out.  It is a property of the format, used by the denormal-row tests
+only; evaluate's bounds are unchanged by it.
 """
 import numpy as np
 
 EPS = 2.0 ** -24
+TINY = 2.0 ** -150          # half the spacing of the fp32 subnormals: the absolute error of an underflowing operation
+FINITE, NAN, POS_INF, NEG_INF = 0, 1, 2, 3
 HERE_CASES = (
     # name, kind, T, start, end, n, d, constructor arguments after (start, end, kind), seed
     ("jk_t4", "jk", 4, 0, 4, 37, 12, (3, 12), 11),
@@ -26,6 +42,25 @@ CASES = {c[0]: dict(zip(("name", "kind", "T", "start", "end", "n", "d", "args", 
 
 def in_dim(kind, T, d):
     return {"gate": d, "ori_ref": 2 * d, "jk": T * d + d}[kind]
+
+
+def underflow_allowance(ops):
+    """What `ops` fp32 operations whose exact results may lie below 2^-126 add to an absolute bound."""
+    return ops * TINY
+
+
+def _zmul(x, y):
+    """x * y for a value x >= 0 and a bound y >= 0, with 0 * inf = 0: the cases where x is exactly 0 in fp32 and
+    in fp64 alike (the module docstring says why each is exact), so nothing of y reaches the result."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where((x == 0) & np.isposinf(y), 0.0, x * y)
+
+
+def classes(x):
+    """An int array of x's shape: FINITE 0, NAN 1, POS_INF 2, NEG_INF 3."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(np.isnan(x), NAN, np.where(np.isposinf(x), POS_INF, np.where(np.isneginf(x), NEG_INF, FINITE))).astype(np.int8)
 
 
 def rows_per_group(n):
@@ -80,7 +115,7 @@ def evaluate(kind, hops, start, end, w, b, G=None, pairing=None, jacobian=True, 
     # a = 1 / (1 + u), u = exp(-S): u is off by the score's error and the exp's 2 eps, relative, which
     # reach a scaled by u / (1 + u) = 1 - a; the add and the divide round once each
     a = 1.0 / (1.0 + np.exp(-S))
-    E_a = a * (1.0 - a) * (E_S + 2 * EPS) + 2 * EPS * a
+    E_a = _zmul(a * (1.0 - a), E_S + 2 * EPS) + 2 * EPS * a
     # e = exp(a), relative: a's error, 2 eps
     e = np.exp(a)
     r_e = E_a + 2 * EPS
@@ -113,7 +148,7 @@ def evaluate(kind, hops, start, end, w, b, G=None, pairing=None, jacobian=True, 
     else:
         j, E_j = np.ones_like(a), np.zeros_like(a)
     dS = da * j
-    E_dS = E_da * j + np.abs(da) * E_j + EPS * np.abs(dS)
+    E_dS = _zmul(j, E_da) + np.abs(da) * E_j + EPS * np.abs(dS)
     dz, E_dz = _unpair(dS, flat), _unpair(E_dS, flat)
 
     # the two reduction stages: a term passes through at most (rows of its group) adds in stage 1 and
@@ -155,6 +190,25 @@ def check(what, got_out, got_dw, got_db, ref):
     assert r[0] <= 1.0, f"{what}: out at {r[0]:.3f} of the bound"
     assert r[1] <= 1.0, f"{what}: weight gradient at {r[1]:.3f} of the bound"
     assert r[2] <= 1.0, f"{what}: bias gradient at {r[2]:.3f} of the bound"
+    return r
+
+
+def check_special(what, got, want, bound):
+    """For results that hold non-finite values on purpose: the class of every element of `got` is `want`'s, and
+    where that class is finite |got - want| <= bound (which must be finite there).  Prints and returns the worst
+    finite ratio."""
+    want = np.asarray(want, dtype=np.float64)
+    got = np.asarray(got, dtype=np.float64).reshape(want.shape)
+    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), want.shape)
+    cg, cw = classes(got), classes(want)
+    bad = np.argwhere(cg != cw)
+    assert bad.size == 0, (f"{what}: {len(bad)} elements of another class (0 finite, 1 NaN, 2 +Inf, 3 -Inf), first at "
+                           f"{tuple(bad[0])}: got {cg[tuple(bad[0])]}, expected {cw[tuple(bad[0])]}")
+    fin = cw == FINITE
+    assert np.isfinite(bound[fin]).all(), f"{what}: a bound is not finite where its value is"
+    r = worst_ratio(got[fin], want[fin], bound[fin])
+    print(f"special values |got - exact| / bound  {what}: {r:.4f} over {int(fin.sum())} finite of {fin.size} elements")
+    assert r <= 1.0, f"{what}: a finite element at {r:.3f} of the bound"
     return r
 
 

@@ -12,10 +12,18 @@ The reference combines the panels and then takes the dot product with w_c; the d
 q_j = w_c . F_j and then combines them.  Both are sums of the i * d triple products W_j * w_c[c] * F_j[., c], in
 different orders, so r_i is bounded as such a sum taken in any order, plus the error carried in W(i-1).
 Nothing here is fitted to a result: every constant counts operations of the formula.
+
+Special values ("Special values and saturation").  A bound is finite wherever its value is
+finite; the zero factors that meet an infinite bound are exact for the reasons of hop_attention_ref: at
+s = +-inf (an Inf cell in a panel) g = 1 / (1 + exp(-s)) is exactly 1 or 0 in both precisions, so
+g (1 - g) (E_s + 2 eps) and g (1 - g) times a bound are 0; and W(0) = softmax([g_0]) is the constant 1 for every g_0
+that is not NaN, so its zero bound times |q_0| = inf is 0.  Where s_0 = p_0 + q_0 + b is NaN the reference's
+one-column softmax is NaN and so is the whole row: W(0) = NaN there, not 1.  classes, check_special and underflow_allowance are hop_attention_ref's.
 """
 import numpy as np
 
-from hop_attention_ref import EPS, rows_per_group, worst_ratio  # noqa: F401
+from hop_attention_ref import (EPS, _zmul, check_special, classes, rows_per_group, underflow_allowance,  # noqa: F401
+                               worst_ratio)
 
 HERE_CASES = (
     # name, T, end, n, d, seed
@@ -60,8 +68,11 @@ def evaluate(hops, end, w, b, G=None, nested=True, swap_halves=False, jacobian=T
     E_zp, E_zq = d * EPS * pa, d * EPS * qa
 
     # forward recurrence; Ws[i] / EWs[i]: [i + 1, n]
-    Ws, EWs = [np.ones((1, n))], [np.zeros((1, n))]
+    # W(0) = softmax([g_0]): exactly 1 for every g_0 but NaN, which the reference's one-column softmax hands on
+    s0 = p[0] + q[0] + b
+    Ws, EWs = [np.where(np.isnan(s0), np.nan, 1.0)[None]], [np.zeros((1, n))]
     g, E_g = np.zeros((H, n)), np.zeros((H, n))
+    sc = np.zeros((H, n))           # the gate scores s_1 .. s_{H-1} (row 0 unused)
     graw = None
     if not nested:
         graw = [1.0 / (1.0 + np.exp(-(p[0] + q[0] + b)))]
@@ -70,10 +81,11 @@ def evaluate(hops, end, w, b, G=None, nested=True, swap_halves=False, jacobian=T
         # s = p_i + sum_{j<i} W_j q_j + b: d products, i d triple products and the bias, in any order
         r = (W * q[:i]).sum(axis=0)
         s = p[i] + r + b
-        E_s = (d + i * d + 2) * EPS * (pa[i] + (W * qa[:i]).sum(axis=0) + abs(b)) + (EW * np.abs(q[:i])).sum(axis=0)
+        sc[i] = s
+        E_s = (d + i * d + 2) * EPS * (pa[i] + (W * qa[:i]).sum(axis=0) + abs(b)) + _zmul(EW, np.abs(q[:i])).sum(axis=0)
         # g = 1 / (1 + u), u = exp(-s): as a of hop_attention_ref
         g[i] = 1.0 / (1.0 + np.exp(-s))
-        E_g[i] = g[i] * (1.0 - g[i]) * (E_s + 2 * EPS) + 2 * EPS * g[i]
+        E_g[i] = _zmul(g[i] * (1.0 - g[i]), E_s + 2 * EPS) + 2 * EPS * g[i]
         if nested:
             x, E_x = np.vstack([W, g[i][None]]), np.vstack([EW, E_g[i][None]])
         else:
@@ -91,7 +103,7 @@ def evaluate(hops, end, w, b, G=None, nested=True, swap_halves=False, jacobian=T
     out = sum(P[:, h:h + 1] * F[h] for h in range(H))
     scale = sum(P[:, h:h + 1] * A[h] for h in range(H))
     E_out = sum(E_P[:, h:h + 1] * A[h] for h in range(H)) + H * EPS * scale
-    res = dict(zp=p, zq=q, E_zp=E_zp, E_zq=E_zq, P=P, E_P=E_P, out=out, E_out=E_out, scale=scale, g=g, Ws=Ws)
+    res = dict(zp=p, zq=q, E_zp=E_zp, E_zq=E_zq, P=P, E_P=E_P, out=out, E_out=E_out, scale=scale, g=g, Ws=Ws, s=sc)
     if G is None:
         return res
 
@@ -117,7 +129,7 @@ def evaluate(hops, end, w, b, G=None, nested=True, swap_halves=False, jacobian=T
         else:
             jac, E_jac = np.ones(n), np.zeros(n)
         ds = dx[i] * jac
-        E_ds = E_dx[i] * jac + np.abs(dx[i]) * E_jac + EPS * np.abs(ds)
+        E_ds = _zmul(jac, E_dx[i]) + np.abs(dx[i]) * E_jac + EPS * np.abs(ds)
         dp[i], E_dp[i] = ds, E_ds
         if drop_dq:
             dW, E_dW = dx[:i], E_dx[:i]
