@@ -794,6 +794,79 @@ int srg_sddmm_rowsum_f32(const int64_t* indptr, const int32_t* indices, const fl
                          const float* G, int64_t ldg, const float* P, int64_t ldp, int32_t d, float* out,
                          void* stream);
 
+/* ---- edge augmentation: nearest sampled candidates per node ----------------------------------------
+ * edge_augument (SSRG/data_augument.py:73-103, helpers utils.py:29-38) gives every low-degree node edges to
+ * the nearest of its randomly drawn candidate nodes, nearest in the L2 distance between feature rows.  The
+ * two entries below are its per-node work for all low-degree nodes at once (srgnn.augment does the rest
+ * with device sorts): the draw of the candidates and the distance + selection. */
+
+/* Candidates per query row at most (the row's distance keys stay in LDS: 16 KiB per wave at the cap);
+ * 4,096 = degree_level 40 at the reference's 100 candidates per missing edge. */
+#define SRG_KNN_MAX_CAND 4096
+/* Feature columns at most (the query row is kept in LDS beside the keys). */
+#define SRG_KNN_MAX_D 8192
+/* Query rows per kernel launch of both entries; more rows go out in further launches on the same stream.
+ * Part of no result -- every row is computed alone -- and stated here so that a test can cross it. */
+#define SRG_KNN_LAUNCH_ROWS 4194304
+
+/* For query row r < n_query: the k_r = out_ptr[r+1] - out_ptr[r] nearest of the candidates
+ * cand[cand_ptr[r] .. cand_ptr[r+1]) (M_r of them, node ids) to node query[r], nearest first, written to
+ * sel[out_ptr[r] ..) and, when sel_dist is not NULL, their distances to sel_dist[out_ptr[r] ..).
+ * X [n, d] fp32 with row stride ldx >= d in elements (a column window of a wider panel and an unaligned
+ * base are fine); query / cand_ptr / cand / out_ptr / sel: int64 on the device.
+ *
+ * Distance (fp32, nothing fused, every operation rounded to nearest even, nothing flushed):
+ *   t_j = fl(X[q, j] - X[c, j]),  s_j = fl(t_j * t_j),  dist = sqrt(S) correctly rounded,
+ * where S adds the s_j in this order, a function of d alone:
+ *   P = ceil(d / 4) pieces of 4 consecutive columns; G = the smallest power of two >= P, at most 64.
+ *   Partial sum p_g, g < G, takes the pieces g, g + G, g + 2G, ... in that order and inside a piece the
+ *   columns ascending, as one chain from +0: p_g = (((+0 + s_a) + s_b) + ...); a p_g without columns is +0.
+ *   Then the halving tree: for h = G/2, G/4, ..., 1:  p_g = p_g + p_{g+h} for g < h.  S = p_0.
+ * d == 0: every distance is +0.  A NaN distance is written to sel_dist as 0x7FC00000.
+ *
+ * Order: ascending distance; equal distances (and +0 against +0) by position in the row's candidate list,
+ * earlier first; NaN distances after +Inf, in position order (torch.sort's NaN-last rule); candidates
+ * whose id lies outside [0, n) after all of those, in position order -- such an id is never used as an
+ * address, and its sel_dist is 0x7FC00000.  The same bits whatever M_r, k_r, the position, the stride and
+ * the load path (16-byte loads when X lies on 16 bytes and ldx is a multiple of 4, else 4-byte loads).
+ * No atomics touch the result: run-to-run identical.
+ *
+ * n_query == 0 launches nothing; k_r == 0 and M_r == 0 are legal rows (when no row asks for a result, nothing
+ * is launched after the check and cand / sel may be NULL).  d < 0, d > SRG_KNN_MAX_D, ldx < d,
+ * n < 0: SRG_ERR_INVALID at once.  The pointer arrays are checked on the device before the selection is
+ * launched (this waits for `stream` once): a decreasing cand_ptr or out_ptr, k_r > M_r, query[r] outside
+ * [0, n) or M_r > SRG_KNN_MAX_CAND: SRG_ERR_INVALID with a message, nothing selected.  The selection itself
+ * is asynchronous on `stream`.  The check allocates two status words on `stream`, copies them to the host
+ * and waits, on every call: the entry cannot be captured into a graph, and a caller who has checked the
+ * arrays already still pays one synchronisation.
+ *
+ * The LDS of a wave is sized by the longest candidate list of the whole call (rounded up to 64), not by
+ * its own row's, and a workgroup shrinks from four waves to two or one to stay within 64 KiB.  One list at
+ * the cap (16 KiB of keys per wave) among many short ones therefore lowers the occupancy of every row of the
+ * call: callers with a few very long lists among many short ones do better with one call per length class. */
+int srg_knn_select_f32(const float* X, int64_t ldx, int64_t n, int32_t d, const int64_t* query,
+                       const int64_t* cand_ptr, const int64_t* cand, const int64_t* out_ptr, int64_t n_query,
+                       int64_t* sel, float* sel_dist, void* stream);
+
+/* Draws the candidates: row r < n_query receives M_r = cand_ptr[r+1] - cand_ptr[r] distinct node ids in
+ * [0, n), none equal to query[r], at cand[cand_ptr[r] ..); entry t of row r is a function of (seed, r, t,
+ * n, query[r]) only.  This is NOT the reference's random stream (Python's random.sample over a list it
+ * mutates): it is a keyed bijection of [0, n - 1) evaluated at t = 0 .. M_r - 1, so the ids are distinct by
+ * construction, shifted past the query node (x >= query[r] becomes x + 1).  Integer arithmetic only
+ * (uint64, wrapping), so that a host restates it bit for bit:
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   key = mix(seed + 0x9E3779B97F4A7C15 * (r + 1))
+ *   m = n - 1;  h = the smallest h >= 1 with 4^h >= m;  mask = 2^h - 1
+ *   F_i(R) = mix(key ^ (0xD6E8FEB86659FD93 * (i + 1)) ^ R) & mask
+ *   perm(x): L = x >> h, R = x & mask; four rounds i = 0..3: (L, R) = (R, L ^ F_i(R)); result (L << h) | R
+ *            (a Feistel network: a bijection of [0, 4^h))
+ *   x = perm(t); while x >= m: x = perm(x)   (cycle walking: t < m, so the walk returns below m)
+ * query[r] outside [0, n), a decreasing cand_ptr or M_r > n - 1: SRG_ERR_INVALID, checked on the device
+ * before the draw is launched (the same check as above: it waits for `stream` once, so no graph capture).
+ * n_query == 0 launches nothing. */
+int srg_sample_distinct_i64(const int64_t* query, const int64_t* cand_ptr, int64_t n_query, int64_t n,
+                            uint64_t seed, int64_t* cand, void* stream);
+
 /* ---- multi-GPU: communicators and the row-partitioned K-hop propagation ---------------------------
  * SURVEY.md §8(b) item 5, for C / C++ hosts (the Python package drives the same kernels through
  * torch.distributed: srgnn/dist.py).  RCCL is loaded at run time.  Rank r owns rows

@@ -54,6 +54,10 @@ SRG_HOP_PAIR_FLAT = 1
 
 SRG_SPGEMM_SERIAL_B = 0x1
 
+SRG_KNN_MAX_CAND = 4096
+SRG_KNN_MAX_D = 8192
+SRG_KNN_LAUNCH_ROWS = 4194304
+
 SRG_PLAN_MIN_HOPS_TO_CUT = 4
 SRG_PLAN_MIN_HOPS_TO_COMPACT = 6
 SRG_PLAN_COMPACT = 0x1
@@ -138,6 +142,8 @@ EXPORTED_SYMBOLS = (
     "srg_sddmm_f32",
     "srg_spmm_scaled_f32",
     "srg_sddmm_rowsum_f32",
+    "srg_knn_select_f32",
+    "srg_sample_distinct_i64",
     "srg_hub_join",
     "srg_hub_side_streams",
     "srg_csr_col_splits",
@@ -291,6 +297,10 @@ def _declare(lib):
     lib.srg_spmm_scaled_f32.restype = ctypes.c_int
     lib.srg_sddmm_rowsum_f32.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _p, _p]
     lib.srg_sddmm_rowsum_f32.restype = ctypes.c_int
+    lib.srg_knn_select_f32.argtypes = [_p, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p]
+    lib.srg_knn_select_f32.restype = ctypes.c_int
+    lib.srg_sample_distinct_i64.argtypes = [_p, _p, _i64, _i64, ctypes.c_uint64, _p, _p]
+    lib.srg_sample_distinct_i64.restype = ctypes.c_int
     lib.srg_hub_join.argtypes = [_p]
     lib.srg_hub_join.restype = ctypes.c_int
     lib.srg_hub_side_streams.argtypes = []
