@@ -867,6 +867,38 @@ int srg_knn_select_f32(const float* X, int64_t ldx, int64_t n, int32_t d, const 
 int srg_sample_distinct_i64(const int64_t* query, const int64_t* cand_ptr, int64_t n_query, int64_t n,
                             uint64_t seed, int64_t* cand, void* stream);
 
+/* ---- graph convolution restricted to a batch of rows ------------------------------------------------
+ * The reference's GCN (Layer2GraphConvolution, SSRG/models/simple_models.py) multiplies by the whole
+ * operator in its last layer and reads output[idx] only.  The two entries below are that product for the
+ * batch's rows alone and its adjoint (srgnn.graph_conv); the full products go through the
+ * planned hop.  fp32; CSR as for srg_spmm_csr_f32 (indptr int64 from 0 to nnz, indices int32, trusted);
+ * panels are row-major with row strides in elements, >= d (column windows and unaligned bases are fine).
+ * Neither entry uses atomics or scratch: run-to-run identical.  16-byte loads when d and both strides are
+ * multiples of 4 and both panels lie on 16 bytes, else 4-byte loads: the same bits either way.  A row is
+ * one wave's serial chain, so a row of L entries costs its length whatever else runs.
+ * Both are asynchronous on `stream` and make no host synchronisation. */
+
+/* Y[b, :] = A[rows[b], :] X for b < B: per element the chain acc = fmaf(values[e], X[indices[e], j], acc)
+ * over row rows[b]'s entries in stored order from +0.0f -- the bits of srg_spmm_csr_f32 for that row.
+ * rows: int64 [B] on the device, in any order, repeats allowed.  An id outside [0, n_rows) gives a row of
+ * +0 and is never used as an address.  X [n_cols, d], ldx; Y [B, d], ldy.  B == 0 or d == 0 is a no-op. */
+int srg_gconv_rows_f32(const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows,
+                       const int64_t* rows, int64_t B, const float* X, int64_t ldx, float* Y, int64_t ldy,
+                       int32_t d, void* stream);
+
+/* The adjoint: dX = A[rows, :]^T G over the rows of the transposed operator (indptr_t, indices_t, values_t;
+ * n rows, column ids in [0, n)).  pos: int32 [n] on the device, pos[r] = b where rows[b] = r and -1 where r
+ * is not in the batch (the ids of a batch are unique).  For every row c < n,
+ *   dX[c, j] = chain over row c's entries e in stored order, from +0.0f, of
+ *              acc = fmaf(values_t[e], G[pos[indices_t[e]], j], acc)
+ * taken over the entries with pos[indices_t[e]] in [0, B) only.  Every other entry is skipped, not
+ * multiplied by zero: an Inf or NaN value outside the batch does not reach dX.  A row without a member
+ * entry is +0; all n rows are written.  A column id outside [0, n) and a position outside [0, B) are never
+ * used as addresses.  G [B, d], ldg; dX [n, d], ldx.  n == 0 or d == 0 is a no-op; B == 0 writes +0. */
+int srg_gconv_rows_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t, const float* values_t, int64_t n,
+                               const int32_t* pos, int64_t B, const float* G, int64_t ldg, float* dX, int64_t ldx,
+                               int32_t d, void* stream);
+
 /* ---- multi-GPU: communicators and the row-partitioned K-hop propagation ---------------------------
  * SURVEY.md §8(b) item 5, for C / C++ hosts (the Python package drives the same kernels through
  * torch.distributed: srgnn/dist.py).  RCCL is loaded at run time.  Rank r owns rows

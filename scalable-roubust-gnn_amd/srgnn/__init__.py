@@ -7,6 +7,7 @@ yyysyyy/Scalable-Roubust-GNN.
     normalize construct_adj on the GPU (bit-exact to SSRG/operators/utils.py:81-93)
     wavelet   Chebyshev heat-kernel filter bank (SpectralModel's wavelet basis)
     wavelet_conv  the wavelet layers' filter phi diag(theta) phi^-1 Z without its n x n product, with autograd
+    graph_conv    GCN's sparse products with autograd: the exact hop both ways, row-restricted for the last layer
     dist      1-D row partition over torch.distributed (RCCL over xGMI), one process per GPU
     synth     deterministic synthetic graphs / features (counter-based hash, CPU == GPU)
     roofline  byte models of SURVEY.md §8(d)

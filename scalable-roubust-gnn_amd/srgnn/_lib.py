@@ -144,6 +144,8 @@ EXPORTED_SYMBOLS = (
     "srg_sddmm_rowsum_f32",
     "srg_knn_select_f32",
     "srg_sample_distinct_i64",
+    "srg_gconv_rows_f32",
+    "srg_gconv_rows_adjoint_f32",
     "srg_hub_join",
     "srg_hub_side_streams",
     "srg_csr_col_splits",
@@ -301,6 +303,10 @@ def _declare(lib):
     lib.srg_knn_select_f32.restype = ctypes.c_int
     lib.srg_sample_distinct_i64.argtypes = [_p, _p, _i64, _i64, ctypes.c_uint64, _p, _p]
     lib.srg_sample_distinct_i64.restype = ctypes.c_int
+    lib.srg_gconv_rows_f32.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _p]
+    lib.srg_gconv_rows_f32.restype = ctypes.c_int
+    lib.srg_gconv_rows_adjoint_f32.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _p]
+    lib.srg_gconv_rows_adjoint_f32.restype = ctypes.c_int
     lib.srg_hub_join.argtypes = [_p]
     lib.srg_hub_join.restype = ctypes.c_int
     lib.srg_hub_side_streams.argtypes = []
