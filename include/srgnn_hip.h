@@ -899,6 +899,65 @@ int srg_gconv_rows_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t
                                const int32_t* pos, int64_t B, const float* G, int64_t ldg, float* dX, int64_t ldx,
                                int32_t d, void* stream);
 
+/* ---- graph attention: the aggregation of a GAT layer, forward and backward --------------------------
+ * GATConv's aggregation (srgnn.gat) is a sparse product whose values are a softmax, over
+ * each target's incoming edges, of a leaky-ReLU score per edge and head.  A is a CSR over targets: row
+ * i < n_rows holds the sources j in [0, n_src) of i's incoming edges (indptr int64 from 0 to nnz, trusted;
+ * indices int32, NOT trusted: an id outside [0, n_src) is skipped everywhere and never used as an address).
+ * Hf [n_src, H*C] (row stride ldh) holds the transformed features, heads side by side; a_src [n_src, H] and
+ * a_dst [n_rows, H] are contiguous.  Per row i, head h, over the row's valid entries e with source j_e:
+ *   s_e = a_src[j_e,h] + a_dst[i,h];  l_e = s_e > 0 ? s_e : slope * s_e;  m = max_e l_e;  p_e = expf(l_e - m)
+ *   z = sum_e p_e;  acc[c] = fmaf(p_e, Hf[j_e,h*C+c], acc[c]) from +0.0f in stored order;  out = acc / z.
+ * Row sums of length L (z, da_dst, da_src) are taken in this order, a function of the positions alone: lane
+ * l of 64 adds the terms at positions l, l + 64, ... in that order from +0.0f, then p_l = p_l + p_{l+w} for
+ * l < w, w = 32, 16, ..., 1; the sum is p_0.  Sums over a head's C columns (D, dalpha) are one fmaf chain
+ * from +0.0f, columns ascending.  Nothing uses atomics, allocates or synchronises; every result is run-to-run
+ * identical, the same with 16-byte loads (C and the strides multiples of 4, bases on 16 bytes) as with
+ * 4-byte loads, and head h of an H-head call has the bits of a one-head call on that head's columns.
+ * A row is one wave's serial work (DESIGN.md 5.11 states a long row's cost).  Asynchronous on `stream`. */
+
+/* Heads at most. */
+#define SRG_GAT_MAX_HEADS 32
+/* H * C at most (the width of a row of Hf, out, G and dHf). */
+#define SRG_GAT_MAX_WIDTH 65536
+/* Rows (and per-row-and-head items) per kernel launch of the three entries; more go out in further launches
+ * on the same stream.  Part of no result; stated here so that a test can cross it. */
+#define SRG_GAT_LAUNCH_ROWS 4194304
+
+/* out [n_rows, H*C] (row stride ldo), M [n_rows, H] = m and Z [n_rows, H] = z, both kept for the backward.
+ * A row without a valid entry gives out = +0, M = 0, Z = 0.  n_rows == 0 is a no-op; nnz == 0 or n_src == 0
+ * launches no kernel and zeroes out, M and Z.  H outside [1, SRG_GAT_MAX_HEADS], C < 1,
+ * H*C > SRG_GAT_MAX_WIDTH, a row stride < H*C, a negative size: SRG_ERR_INVALID. */
+int srg_gat_attend_f32(const int64_t* indptr, const int32_t* indices, int64_t nnz, int64_t n_rows, int64_t n_src,
+                       const float* a_src, const float* a_dst, float slope, const float* Hf, int64_t ldh, int32_t H,
+                       int32_t C, float* out, int64_t ldo, float* M, float* Z, void* stream);
+
+/* The per-edge part of the backward, with G = dL/dout [n_rows, H*C] (row stride ldg) and out, M, Z as the
+ * forward left them; alpha_e = expf(l_e - M[i,h]) / Z[i,h]:
+ *   D[i,h]  = chain over c of G[i,h*C+c] * out[i,h*C+c]                 (scratch [n_rows, H] of the caller)
+ *   ds[e,h] = (alpha_e * (chain over c of G[i,h*C+c] * Hf[j_e,h*C+c] - D[i,h])) * (s_e > 0 ? 1 : slope)
+ *             written to dS [nnz, H] in A's order; +0 for a skipped entry
+ *   da_dst[i,h] = the row sum of ds[., h] over row i.
+ * n_rows == 0 is a no-op; nnz == 0 or n_src == 0 zeroes da_dst and launches nothing. */
+int srg_gat_edge_grad_f32(const int64_t* indptr, const int32_t* indices, int64_t nnz, int64_t n_rows, int64_t n_src,
+                          const float* a_src, const float* a_dst, float slope, const float* Hf, int64_t ldh,
+                          int32_t H, int32_t C, const float* out, int64_t ldo, const float* M, const float* Z,
+                          const float* G, int64_t ldg, float* D, float* dS, float* da_dst, void* stream);
+
+/* The part of the backward that runs over the transpose At (n_src rows; indices_t are targets in
+ * [0, n_rows), skipped when outside) and perm (entry t of At is entry perm[t] of A; an index outside
+ * [0, nnz) is skipped):
+ *   dHf[j,h*C+c] = chain from +0.0f over row j of At in stored order of fmaf(alpha_t, G[i_t,h*C+c], .)
+ *   da_src[j,h]  = the row sum over row j of At of dS[perm[t], h]
+ * A target whose Z[i,h] is 0 (a row of A without a valid entry, which a consistent At never names) adds
+ * nothing to dHf; srg_gat_edge_grad_f32 writes ds = +0 for the entries of such a row.
+ * Either result may be NULL and is then not computed (dS and perm are read for da_src only; a_src, a_dst,
+ * M, Z and G for dHf only).  n_src == 0 is a no-op; nnz == 0 or n_rows == 0 zeroes the results. */
+int srg_gat_attend_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t, const int64_t* perm, int64_t nnz,
+                               int64_t n_rows, int64_t n_src, const float* a_src, const float* a_dst, float slope,
+                               int32_t H, int32_t C, const float* M, const float* Z, const float* G, int64_t ldg,
+                               const float* dS, float* dHf, int64_t ldd, float* da_src, void* stream);
+
 /* ---- multi-GPU: communicators and the row-partitioned K-hop propagation ---------------------------
  * SURVEY.md §8(b) item 5, for C / C++ hosts (the Python package drives the same kernels through
  * torch.distributed: srgnn/dist.py).  RCCL is loaded at run time.  Rank r owns rows

@@ -58,6 +58,10 @@ SRG_KNN_MAX_CAND = 4096
 SRG_KNN_MAX_D = 8192
 SRG_KNN_LAUNCH_ROWS = 4194304
 
+SRG_GAT_MAX_HEADS = 32
+SRG_GAT_MAX_WIDTH = 65536
+SRG_GAT_LAUNCH_ROWS = 4194304
+
 SRG_PLAN_MIN_HOPS_TO_CUT = 4
 SRG_PLAN_MIN_HOPS_TO_COMPACT = 6
 SRG_PLAN_COMPACT = 0x1
@@ -146,6 +150,9 @@ EXPORTED_SYMBOLS = (
     "srg_sample_distinct_i64",
     "srg_gconv_rows_f32",
     "srg_gconv_rows_adjoint_f32",
+    "srg_gat_attend_f32",
+    "srg_gat_edge_grad_f32",
+    "srg_gat_attend_adjoint_f32",
     "srg_hub_join",
     "srg_hub_side_streams",
     "srg_csr_col_splits",
@@ -307,6 +314,14 @@ def _declare(lib):
     lib.srg_gconv_rows_f32.restype = ctypes.c_int
     lib.srg_gconv_rows_adjoint_f32.argtypes = [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _p]
     lib.srg_gconv_rows_adjoint_f32.restype = ctypes.c_int
+    lib.srg_gat_attend_f32.argtypes = [_p, _p, _i64, _i64, _i64, _p, _p, _f32, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]
+    lib.srg_gat_attend_f32.restype = ctypes.c_int
+    lib.srg_gat_edge_grad_f32.argtypes = [_p, _p, _i64, _i64, _i64, _p, _p, _f32, _p, _i64, _i32, _i32, _p, _i64, _p, _p,
+                                          _p, _i64, _p, _p, _p, _p]
+    lib.srg_gat_edge_grad_f32.restype = ctypes.c_int
+    lib.srg_gat_attend_adjoint_f32.argtypes = [_p, _p, _p, _i64, _i64, _i64, _p, _p, _f32, _i32, _i32, _p, _p, _p, _i64,
+                                               _p, _p, _i64, _p, _p]
+    lib.srg_gat_attend_adjoint_f32.restype = ctypes.c_int
     lib.srg_hub_join.argtypes = [_p]
     lib.srg_hub_join.restype = ctypes.c_int
     lib.srg_hub_side_streams.argtypes = []
