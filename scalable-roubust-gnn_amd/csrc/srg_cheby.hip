@@ -458,19 +458,18 @@ int launch_cheby(const int64_t* indptr, const int32_t* indices, const T* vals, i
                         ? 2
                         : 1;
     const int nr = (int)n_rows;
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxLaunchBlocks) {
-        const dim3 grid((unsigned)std::min<int64_t>(kMaxLaunchBlocks, blocks - b0));
+    rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (vec == 2)
-            hipLaunchKernelGGL((k_cheby<T, 2, kUnroll>), grid, dim3(kBlock), 0, s, indptr, indices,
+            hipLaunchKernelGGL((k_cheby<T, 2, kUnroll>), dim3(nb), dim3(kBlock), 0, s, indptr, indices,
                                vals, order, nr, Tc, To, Tn, ld, d, mode, a1, a2, cf, n_scales, R,
                                r_stride, (int)b0);
         else
-            hipLaunchKernelGGL((k_cheby<T, 1, kUnroll>), grid, dim3(kBlock), 0, s, indptr, indices,
+            hipLaunchKernelGGL((k_cheby<T, 1, kUnroll>), dim3(nb), dim3(kBlock), 0, s, indptr, indices,
                                vals, order, nr, Tc, To, Tn, ld, d, mode, a1, a2, cf, n_scales, R,
                                r_stride, (int)b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    SRG_HIP_CHECK(hipGetLastError());
+        return launch_status();
+    });
+    if (rc) return rc;
     if (!nojoin)
         if (int rc = hub.join()) return rc;
     return srg_ok();
@@ -598,10 +597,9 @@ __attribute__((visibility("hidden"))) int srg_run_plan_cheby_f64(const srg_hop_l
         const int64_t blocks = (L.n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
         const int nr = (int)L.n_rows;
         // (uncapped: 4 or 6 waves per SIMD measured 0.5-3 % slower, profiles/r06i_cheby64_plan_sweep.txt)
-        for (int64_t b0 = 0; b0 < blocks; b0 += kMaxLaunchBlocks) {
-            const dim3 grid((unsigned)std::min<int64_t>(kMaxLaunchBlocks, blocks - b0));
+        const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
 #define SRG_LAUNCH_BLK64(V, F, LA)                                                                                \
-    hipLaunchKernelGGL((k_cheby_blk64<V, kUnroll, F, LA>), grid, dim3(kBlock), 0, s, L.slot_beg, L.slot_end,     \
+    hipLaunchKernelGGL((k_cheby_blk64<V, kUnroll, F, LA>), dim3(nb), dim3(kBlock), 0, s, L.slot_beg, L.slot_end, \
                        L.row_order, nr, indices, values, Tc, To, Tn, ld, d, mode, a1, a2, cf, n_scales, R, r_stride, \
                        (int)b0)
 #define SRG_LAUNCH_BLK64_V(F, LA)                  \
@@ -617,8 +615,9 @@ __attribute__((visibility("hidden"))) int srg_run_plan_cheby_f64(const srg_hop_l
             }
 #undef SRG_LAUNCH_BLK64_V
 #undef SRG_LAUNCH_BLK64
-            SRG_HIP_CHECK(hipGetLastError());
-        }
+            return launch_status();
+        });
+        if (rc) return rc;
     }
     if (int rc = hub.join()) return rc;
     return srg_ok();

@@ -1,13 +1,15 @@
 // srg_device.h -- device code that more than one kernel family uses: vector loads and stores, the chain
-// link and the epilogue arithmetic, the row-wave gather, the launch constants; and the host checks that go
-// with them.  Everything is in the anonymous namespace: each translation unit that includes this header
-// compiles its own copy into its own kernels.  Not part of the C-ABI (include/srgnn_hip.h).
+// link and the epilogue arithmetic, the row-wave gather, the filtered row walk, the launch constants; and
+// the host checks that go with them, the vector-width check among them.  Everything is in the anonymous
+// namespace: each translation unit that includes this header compiles its own copy into its own kernels.
+// Not part of the C-ABI (include/srgnn_hip.h).
 #ifndef SRG_DEVICE_H_
 #define SRG_DEVICE_H_
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 
 #include "srgnn_hip.h"
 #include "srg_internal.h"
@@ -186,17 +188,63 @@ __device__ __forceinline__ void row_gather(typename Vec<T, VEC>::type& acc,
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// the filtered row walk: the chain over the kept entries of indices[beg, end), in stored order
+//
+// Lanes across entries for the filter, lanes across columns for the chain.  The row's ids are read 64 at
+// a time (lane l holds entry jb + l, -1 past the row's end), the next 64 while this block is walked.
+// keep(id, j) is the lane's verdict on its entry j: a small struct with `kept` and whatever the lane
+// derived from the entry.  It must reject every id outside its table's range before it or fetch uses one
+// as an address.  One ballot collects the verdicts and is walked from its lowest set bit, so the chain
+// keeps the stored order.  fetch(mine, q) broadcasts lane q's struct (v_readlane: q is wave-uniform) and
+// issues that entry's loads into a Slot; U slots are in flight, then fold(slot) runs the chain links in
+// order.  (fetch broadcasts what the lane itself loaded in keep before it issues a gather: the wait for
+// that load would otherwise come to stand behind the slot's first gather.)  Slots past the last kept entry repeat it (always a valid address) and are skipped by a
+// wave-uniform predicate; they, like the entries not kept, are never folded in as 0 * x: that would flip
+// -0.0 sums and turn inf/nan inputs into nan.
+// Cost of a long row: a row is one wave's serial chain.  A row of L entries of which M are kept costs
+// L / 64 rounds of (ids -> verdicts -> ballot) plus M / U gather rounds, whatever the other waves do.
+// ------------------------------------------------------------------------------------------------
+template <typename Slot, int U, typename Keep, typename Fetch, typename Fold>
+__device__ __forceinline__ void row_walk_kept(const int32_t* __restrict__ indices, int64_t beg, int64_t end,
+                                              Keep keep, Fetch fetch, Fold fold)
+{
+    if (beg >= end) return;
+    const int lane = threadIdx.x & 63;
+    int64_t j0 = beg + lane;
+    int id_nxt = j0 < end ? indices[j0] : -1;
+    for (int64_t jb = beg; jb < end; jb += 64) {
+        const int id = id_nxt;
+        const int64_t jn = jb + 64 + lane;
+        id_nxt = jn < end ? indices[jn] : -1;
+        const auto mine = keep(id, jb + lane);
+        unsigned long long mask = __ballot(mine.kept);
+        while (mask) {
+            const int live = __builtin_popcountll(mask);
+            const int cnt = live < U ? live : U;   // wave-uniform
+            Slot s[U];
+            int q = 0;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (mask) {
+                    q = __builtin_ctzll(mask);
+                    mask &= mask - 1;
+                }
+                s[u] = fetch(mine, q);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (u < cnt) fold(s[u]);
+        }
+    }
+}
+
 __device__ __forceinline__ int wave_slot(int block_base)
 {
     // wave-uniform by construction; readfirstlane makes that provable to the compiler so that the
     // row's index stream goes through the scalar path.
     return __builtin_amdgcn_readfirstlane((int)((block_base + (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6)));
 }
-
-// A dispatch holds < 2^32 work-items per dimension: launches of more rows than that (111 M rows
-// of the papers100M-shaped graph = 7.1e9 lanes) go out in chunks of kMaxLaunchBlocks blocks, the
-// kernel adding the chunk's block_base to blockIdx.x.
-constexpr int64_t kMaxLaunchBlocks = int64_t(1) << 23;
 
 // ------------------------------------------------------------------------------------------------
 // launch helpers
@@ -205,15 +253,24 @@ constexpr int kUnroll = 8;
 
 bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// May rows be read and written v elements of `elem` bytes at a time: d is whole accesses, and every row of
+// every operand (base pointer, row stride in elements) starts on one.
+struct Operand {
+    const void* p;
+    int64_t ld;
+};
+bool rows_aligned(int v, size_t elem, int d, std::initializer_list<Operand> ops)
+{
+    bool ok = d % v == 0;
+    for (const Operand& o : ops) ok = ok && o.ld % v == 0 && aligned(o.p, v * elem);
+    return ok;
+}
+
 int pick_vec(int d, int64_t ldx, int64_t ldy, const void* X, const void* Y, size_t elem)
 {
     // widest per-lane access whose tiles line up with every row of X and Y
-    if (elem == 4 && d >= 256 && d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned(X, 16) &&
-        aligned(Y, 16))
-        return 4;
-    if (d >= 128 && d % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && aligned(X, 2 * elem) &&
-        aligned(Y, 2 * elem))
-        return 2;
+    if (elem == 4 && d >= 256 && rows_aligned(4, elem, d, {{X, ldx}, {Y, ldy}})) return 4;
+    if (d >= 128 && rows_aligned(2, elem, d, {{X, ldx}, {Y, ldy}})) return 2;
     return 1;
 }
 

@@ -43,7 +43,6 @@
 // the two gathers, and ceil(L H / 64) C-column chains in the edge kernel, whatever the other waves do.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
@@ -55,6 +54,8 @@ namespace {
 
 constexpr int64_t kRowsPerLaunch = SRG_GAT_LAUNCH_ROWS;                    // rows (waves) of one launch
 constexpr int64_t kBlocksPerLaunch = kRowsPerLaunch / kWavesPerBlock;
+static_assert(kRowsPerLaunch % kBlock == 0 && kBlocksPerLaunch <= kMaxLaunchBlocks,
+              "a launch's rows, or (row, head) items, fill whole workgroups and fit one grid");
 
 __device__ __forceinline__ float leaky(float s, float slope) { return s > 0.0f ? s : __fmul_rn(slope, s); }
 
@@ -111,10 +112,15 @@ k_gat_stats(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indi
     }
 }
 
-// out[row, col ..]: the chain over the row's valid entries in stored order, divided by z.  Lanes across
-// entries for the id stream and the validity ballot, lanes across columns for the chain (the walk of
-// k_gconv_rows_adjoint): kUnroll source rows are in flight; slots past the last valid entry repeat it (a valid
-// address) and are skipped by a wave-uniform predicate.
+// a lane's verdict on its entry in both gathers: the id, kept when it is in range (so never an address otherwise)
+struct KeptId {
+    bool kept;
+    int id;
+};
+
+// out[row, col ..]: the chain over the row's valid entries in stored order, divided by z: the filtered row
+// walk (srg_device.h).  keep: the source id, kept when it lies in [0, n_src); fetch: that source's row of Hf
+// and its a_src; fold: p_e and the chain link.
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 k_gat_attend(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, int64_t n_src,
@@ -132,45 +138,19 @@ k_gat_attend(const int64_t* __restrict__ indptr, const int32_t* __restrict__ ind
     const float ad = a_dst[(int64_t)row * H + h];
     const float m = M[(int64_t)row * H + h], z = Z[(int64_t)row * H + h];
     V acc = vzero<float, VEC>();
-    const int64_t beg = indptr[row], end = indptr[row + 1];
-    if (beg < end) {
-        int64_t j0 = beg + lane;
-        int id_nxt = j0 < end ? indices[j0] : -1;
-        for (int64_t jb = beg; jb < end; jb += 64) {
-            const int id = id_nxt;
-            const int64_t jn = jb + 64 + lane;
-            id_nxt = jn < end ? indices[jn] : -1;
-            unsigned long long mask = __ballot(id >= 0 && id < n_src);   // an id outside [0, n_src) is no address
-            while (mask) {
-                const int live = __builtin_popcountll(mask);
-                const int cnt = live < kUnroll ? live : kUnroll;   // wave-uniform
-                V x[kUnroll];
-                float as[kUnroll];
-                int q = 0;
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    if (mask) {
-                        q = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                    }
-                    const int c = __builtin_amdgcn_readlane(id, q);
-                    if (act) {
-                        x[u] = gload<float, VEC>(Hf + (int64_t)c * ldh + col);
-                        as[u] = a_src[(int64_t)c * H + h];
-                    } else {
-                        x[u] = vzero<float, VEC>();
-                        as[u] = 0.0f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u)
-                    if (u < cnt) {
-                        const float p = expf(__fsub_rn(leaky(__fadd_rn(as[u], ad), slope), m));
-                        chain<float, VEC>(acc, p, x[u]);
-                    }
-            }
-        }
-    }
+    struct Slot { V x; float as; };
+    row_walk_kept<Slot, kUnroll>(
+        indices, indptr[row], indptr[row + 1],
+        [&](int id, int64_t) { return KeptId{id >= 0 && id < n_src, id}; },
+        [&](const KeptId& mine, int q) {
+            const int c = __builtin_amdgcn_readlane(mine.id, q);
+            if (!act) return Slot{vzero<float, VEC>(), 0.0f};
+            return Slot{gload<float, VEC>(Hf + (int64_t)c * ldh + col), a_src[(int64_t)c * H + h]};
+        },
+        [&](const Slot& s) {
+            const float p = expf(__fsub_rn(leaky(__fadd_rn(s.as, ad), slope), m));
+            chain<float, VEC>(acc, p, s.x);
+        });
     if (act) {
         V o;
         if constexpr (VEC == 1) {
@@ -184,7 +164,9 @@ k_gat_attend(const int64_t* __restrict__ indptr, const int32_t* __restrict__ ind
 }
 
 // dHf[row, col ..] over row `row` of At: the chain of alpha_t * G[i_t, col ..] over the valid entries in
-// stored order, alpha_t recomputed from the target's a_dst, M and Z.
+// stored order, alpha_t recomputed from the target's a_dst, M and Z: the filtered row walk again.  keep: the
+// target id, kept when it lies in [0, n_rows); fetch: that target's row of G, a_dst, M and Z; fold: alpha_t
+// and the chain link.
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 k_gat_adjoint(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, int64_t n_src,
@@ -201,49 +183,21 @@ k_gat_adjoint(const int64_t* __restrict__ indptr, const int32_t* __restrict__ in
     const int h = act ? col / C : 0;
     const float as = a_src[(int64_t)row * H + h];
     V acc = vzero<float, VEC>();
-    const int64_t beg = indptr[row], end = indptr[row + 1];
-    if (beg < end) {
-        int64_t j0 = beg + lane;
-        int id_nxt = j0 < end ? indices[j0] : -1;
-        for (int64_t jb = beg; jb < end; jb += 64) {
-            const int id = id_nxt;
-            const int64_t jn = jb + 64 + lane;
-            id_nxt = jn < end ? indices[jn] : -1;
-            unsigned long long mask = __ballot(id >= 0 && id < n_rows);   // a target outside [0, n_rows) is no address
-            while (mask) {
-                const int live = __builtin_popcountll(mask);
-                const int cnt = live < kUnroll ? live : kUnroll;   // wave-uniform
-                V x[kUnroll];
-                float ad[kUnroll], mm[kUnroll], zz[kUnroll];
-                int q = 0;
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    if (mask) {
-                        q = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                    }
-                    const int i = __builtin_amdgcn_readlane(id, q);
-                    if (act) {
-                        x[u] = gload<float, VEC>(G + (int64_t)i * ldg + col);
-                        ad[u] = a_dst[(int64_t)i * H + h];
-                        mm[u] = M[(int64_t)i * H + h];
-                        zz[u] = Z[(int64_t)i * H + h];
-                    } else {
-                        x[u] = vzero<float, VEC>();
-                        ad[u] = mm[u] = 0.0f;
-                        zz[u] = 1.0f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u)
-                    if (u < cnt) {
-                        const float p = expf(__fsub_rn(leaky(__fadd_rn(as, ad[u]), slope), mm[u]));
-                        // Z == 0 marks a target without a valid entry (a forged id of At): it contributes nothing
-                        if (zz[u] != 0.0f) chain<float, VEC>(acc, __fdiv_rn(p, zz[u]), x[u]);
-                    }
-            }
-        }
-    }
+    struct Slot { V x; float ad, m, z; };
+    row_walk_kept<Slot, kUnroll>(
+        indices, indptr[row], indptr[row + 1],
+        [&](int id, int64_t) { return KeptId{id >= 0 && id < n_rows, id}; },
+        [&](const KeptId& mine, int q) {
+            const int i = __builtin_amdgcn_readlane(mine.id, q);
+            const int64_t ih = (int64_t)i * H + h;
+            if (!act) return Slot{vzero<float, VEC>(), 0.0f, 0.0f, 1.0f};
+            return Slot{gload<float, VEC>(G + (int64_t)i * ldg + col), a_dst[ih], M[ih], Z[ih]};
+        },
+        [&](const Slot& s) {
+            const float p = expf(__fsub_rn(leaky(__fadd_rn(as, s.ad), slope), s.m));
+            // Z == 0 marks a target without a valid entry (a forged id of At): it contributes nothing
+            if (s.z != 0.0f) chain<float, VEC>(acc, __fdiv_rn(p, s.z), s.x);
+        });
     if (act) vstore<float, VEC>(dHf + (int64_t)row * ldd + col, acc, false);
 }
 
@@ -350,11 +304,6 @@ int check_ld(const char* name, int64_t ld, int W)
     return SRG_OK;
 }
 
-bool vec4_ok(int C, const void* a, int64_t lda, const void* b, int64_t ldb)
-{
-    return C % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned(a, 16) && aligned(b, 16);
-}
-
 }  // namespace
 
 extern "C" {
@@ -379,27 +328,26 @@ int srg_gat_attend_f32(const int64_t* indptr, const int32_t* indices, int64_t nn
     }
     if (!indptr || !indices || !a_src || !a_dst || !Hf)
         return srg_fail(SRG_ERR_INVALID, "null indptr, indices, a_src, a_dst or Hf");
-    const bool v4 = vec4_ok(C, Hf, ldh, out, ldo);
+    const bool v4 = rows_aligned(4, sizeof(float), C, {{Hf, ldh}, {out, ldo}});
     const int tile = v4 ? 256 : 64;
     const unsigned tiles = (unsigned)((W + tile - 1) / tile);
     const int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    for (int64_t b0 = 0; b0 < blocks; b0 += kBlocksPerLaunch) {
-        const unsigned nb = (unsigned)std::min<int64_t>(kBlocksPerLaunch, blocks - b0);
+    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         hipLaunchKernelGGL(k_gat_stats, dim3(nb), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src, a_src, a_dst,
                            slope, (int)H, M, Z, (int)b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    for (int64_t b0 = 0; b0 < blocks; b0 += kBlocksPerLaunch) {
-        const dim3 grid((unsigned)std::min<int64_t>(kBlocksPerLaunch, blocks - b0), tiles);
+        return launch_status();
+    });
+    if (rc) return rc;
+    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         if (v4)
-            hipLaunchKernelGGL(k_gat_attend<4>, grid, dim3(kBlock), 0, s, indptr, indices, n_rows, n_src, a_src, a_dst,
-                               slope, Hf, ldh, (int)H, (int)C, M, Z, out, ldo, (int)b0);
+            hipLaunchKernelGGL(k_gat_attend<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src,
+                               a_src, a_dst, slope, Hf, ldh, (int)H, (int)C, M, Z, out, ldo, (int)b0);
         else
-            hipLaunchKernelGGL(k_gat_attend<1>, grid, dim3(kBlock), 0, s, indptr, indices, n_rows, n_src, a_src, a_dst,
-                               slope, Hf, ldh, (int)H, (int)C, M, Z, out, ldo, (int)b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+            hipLaunchKernelGGL(k_gat_attend<1>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src,
+                               a_src, a_dst, slope, Hf, ldh, (int)H, (int)C, M, Z, out, ldo, (int)b0);
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 int srg_gat_edge_grad_f32(const int64_t* indptr, const int32_t* indices, int64_t nnz, int64_t n_rows, int64_t n_src,
@@ -421,37 +369,36 @@ int srg_gat_edge_grad_f32(const int64_t* indptr, const int32_t* indices, int64_t
     }
     if (!indptr || !indices || !a_src || !a_dst || !Hf || !out || !M || !Z || !G || !D || !dS)
         return srg_fail(SRG_ERR_INVALID, "null operand");
-    const int64_t total = n_rows * H;
-    const bool v4d = vec4_ok(C, G, ldg, out, ldo);
-    for (int64_t t0 = 0; t0 < total; t0 += kRowsPerLaunch) {
-        const unsigned nb = (unsigned)((std::min<int64_t>(kRowsPerLaunch, total - t0) + kBlock - 1) / kBlock);
+    const int64_t total = n_rows * H;   // one thread per item: kRowsPerLaunch items are whole blocks
+    const bool v4d = rows_aligned(4, sizeof(float), C, {{G, ldg}, {out, ldo}});
+    rc = launch_chunks((total + kBlock - 1) / kBlock, kRowsPerLaunch / kBlock, [&](int64_t b0, unsigned nb) {
         if (v4d)
             hipLaunchKernelGGL(k_gat_rowdot<true>, dim3(nb), dim3(kBlock), 0, s, total, (int)H, (int)C, G, ldg, out, ldo,
-                               D, t0);
+                               D, b0 * kBlock);
         else
             hipLaunchKernelGGL(k_gat_rowdot<false>, dim3(nb), dim3(kBlock), 0, s, total, (int)H, (int)C, G, ldg, out,
-                               ldo, D, t0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    const bool v4e = vec4_ok(C, G, ldg, Hf, ldh);
+                               ldo, D, b0 * kBlock);
+        return launch_status();
+    });
+    if (rc) return rc;
+    const bool v4e = rows_aligned(4, sizeof(float), C, {{G, ldg}, {Hf, ldh}});
     const int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    for (int64_t b0 = 0; b0 < blocks; b0 += kBlocksPerLaunch) {
-        const unsigned nb = (unsigned)std::min<int64_t>(kBlocksPerLaunch, blocks - b0);
+    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         if (v4e)
             hipLaunchKernelGGL(k_gat_edge<true>, dim3(nb), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src, nnz, a_src,
                                a_dst, slope, Hf, ldh, (int)H, (int)C, M, Z, G, ldg, D, dS, (int)b0);
         else
             hipLaunchKernelGGL(k_gat_edge<false>, dim3(nb), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src, nnz, a_src,
                                a_dst, slope, Hf, ldh, (int)H, (int)C, M, Z, G, ldg, D, dS, (int)b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    for (int64_t b0 = 0; b0 < blocks; b0 += kBlocksPerLaunch) {
-        const unsigned nb = (unsigned)std::min<int64_t>(kBlocksPerLaunch, blocks - b0);
+        return launch_status();
+    });
+    if (rc) return rc;
+    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         hipLaunchKernelGGL(k_gat_rowsum, dim3(nb), dim3(kBlock), 0, s, indptr, (const int64_t*)nullptr, n_rows, nnz,
                            (int)H, dS, da_dst, (int)b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 int srg_gat_attend_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t, const int64_t* perm, int64_t nnz,
@@ -477,29 +424,27 @@ int srg_gat_attend_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t
     if (da_src && (!perm || !dS)) return srg_fail(SRG_ERR_INVALID, "null perm or dS with da_src");
     const int64_t blocks = (n_src + kWavesPerBlock - 1) / kWavesPerBlock;
     if (dHf) {
-        const bool v4 = vec4_ok(C, G, ldg, dHf, ldd);
+        const bool v4 = rows_aligned(4, sizeof(float), C, {{G, ldg}, {dHf, ldd}});
         const int tile = v4 ? 256 : 64;
         const unsigned tiles = (unsigned)((W + tile - 1) / tile);
-        for (int64_t b0 = 0; b0 < blocks; b0 += kBlocksPerLaunch) {
-            const dim3 grid((unsigned)std::min<int64_t>(kBlocksPerLaunch, blocks - b0), tiles);
+        rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
             if (v4)
-                hipLaunchKernelGGL(k_gat_adjoint<4>, grid, dim3(kBlock), 0, s, indptr_t, indices_t, n_rows, n_src, a_src,
-                                   a_dst, slope, (int)H, (int)C, M, Z, G, ldg, dHf, ldd, (int)b0);
+                hipLaunchKernelGGL(k_gat_adjoint<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr_t, indices_t, n_rows,
+                                   n_src, a_src, a_dst, slope, (int)H, (int)C, M, Z, G, ldg, dHf, ldd, (int)b0);
             else
-                hipLaunchKernelGGL(k_gat_adjoint<1>, grid, dim3(kBlock), 0, s, indptr_t, indices_t, n_rows, n_src, a_src,
-                                   a_dst, slope, (int)H, (int)C, M, Z, G, ldg, dHf, ldd, (int)b0);
-            SRG_HIP_CHECK(hipGetLastError());
-        }
+                hipLaunchKernelGGL(k_gat_adjoint<1>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr_t, indices_t, n_rows,
+                                   n_src, a_src, a_dst, slope, (int)H, (int)C, M, Z, G, ldg, dHf, ldd, (int)b0);
+            return launch_status();
+        });
+        if (rc) return rc;
     }
-    if (da_src) {
-        for (int64_t b0 = 0; b0 < blocks; b0 += kBlocksPerLaunch) {
-            const unsigned nb = (unsigned)std::min<int64_t>(kBlocksPerLaunch, blocks - b0);
+    if (da_src)
+        rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
             hipLaunchKernelGGL(k_gat_rowsum, dim3(nb), dim3(kBlock), 0, s, indptr_t, perm, n_src, nnz, (int)H, dS, da_src,
                                (int)b0);
-            SRG_HIP_CHECK(hipGetLastError());
-        }
-    }
-    return srg_ok();
+            return launch_status();
+        });
+    return rc ? rc : srg_ok();
 }
 
 }  // extern "C"

@@ -10,11 +10,9 @@
 // loads, VEC 1: 4-byte loads) nor the launch.  No atomics, no scratch; every store is a plain vector store.
 //
 // Cost of a long row: a row is one wave's serial chain.  Forward, a batch row of L entries costs L / 8
-// rounds of 8 gathers in flight (row_gather); in the adjoint a row of L entries with M members costs
-// L / 64 rounds of (ids -> positions -> ballot) plus M / 8 gather rounds, whatever the other waves do.
+// rounds of 8 gathers in flight (row_gather); the adjoint's cost is the filtered row walk's (row_walk_kept).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
 
 #include "srgnn_hip.h"
@@ -46,11 +44,9 @@ k_gconv_rows(const int64_t* __restrict__ indptr, const int32_t* __restrict__ ind
     if (act) vstore<float, VEC>(Y + (int64_t)b * ldy + col, acc, false);
 }
 
-// dX[c, col ..] = the chain over row c of the transposed operator, member entries only.  Lanes across
-// entries for the membership test (64 ids, their positions, one ballot), lanes across columns for the
-// chain: the ballot is walked from its lowest set bit, so the chain keeps the stored order.  kUnroll member
-// rows of G are in flight; slots past the last member repeat it (always a valid address) and are skipped
-// by a wave-uniform predicate.  The next 64 ids are loaded while this block is walked.
+// dX[c, col ..] = the chain over row c of the transposed operator, member entries only: the filtered row
+// walk (srg_device.h).  keep: the entry's position pos[id] and value, kept when the position is a member's;
+// fetch: that member's row of G; fold: the chain link.
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 k_gconv_rows_adjoint(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
@@ -65,45 +61,25 @@ k_gconv_rows_adjoint(const int64_t* __restrict__ indptr, const int32_t* __restri
     const int col = ((int)blockIdx.y * 64 + lane) * VEC;
     const bool act = col < d;
     V acc = vzero<float, VEC>();
-    const int64_t beg = indptr[c], end = indptr[c + 1];
-    if (beg < end) {
-        int64_t j0 = beg + lane;
-        int id_nxt = j0 < end ? indices[j0] : -1;
-        for (int64_t jb = beg; jb < end; jb += 64) {
-            const int id = id_nxt;
-            const int64_t j = jb + lane, jn = jb + 64 + lane;
-            id_nxt = jn < end ? indices[jn] : -1;
+    struct Entry { bool kept; int p; float a; };
+    struct Slot { V x; float a; };
+    row_walk_kept<Slot, kUnroll>(
+        indices, indptr[c], indptr[c + 1],
+        [&](int id, int64_t j) {
             // an id outside [0, n) is never an address; a position outside [0, B) is no member
             int p = -1;
             if (id >= 0 && id < n) p = pos[id];
             const bool member = p >= 0 && p < B;
-            const float a_blk = member ? values[j] : 0.0f;
-            unsigned long long mask = __ballot(member);
-            while (mask) {
-                const int m = __builtin_popcountll(mask);
-                const int cnt = m < kUnroll ? m : kUnroll;   // wave-uniform
-                V x[kUnroll];
-                float a[kUnroll];
-                int q = 0;
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    if (mask) {
-                        q = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                    }
-                    const int pq = __builtin_amdgcn_readlane(p, q);
-                    a[u] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a_blk), q));
-                    if (act)
-                        x[u] = gload<float, VEC>(G + (int64_t)pq * ldg + col);
-                    else
-                        x[u] = vzero<float, VEC>();
-                }
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u)
-                    if (u < cnt) chain<float, VEC>(acc, a[u], x[u]);
-            }
-        }
-    }
+            return Entry{member, p, member ? values[j] : 0.0f};
+        },
+        [&](const Entry& mine, int q) {
+            // (the value first: its readlane waits for the lane's load of values[j], which must not come to
+            // stand behind a gather that is already in flight)
+            const int pq = __builtin_amdgcn_readlane(mine.p, q);
+            const float a = bcast_lane(mine.a, q);
+            return Slot{act ? gload<float, VEC>(G + (int64_t)pq * ldg + col) : vzero<float, VEC>(), a};
+        },
+        [&](const Slot& s) { chain<float, VEC>(acc, s.a, s.x); });
     if (act) vstore<float, VEC>(dX + (int64_t)c * ldx + col, acc, false);
 }
 
@@ -116,11 +92,6 @@ int check_sizes(int64_t n, int64_t B, int d, int64_t lda, int64_t ldb, const cha
         return srg_fail(SRG_ERR_INVALID, "leading dimensions (%s=%lld, %s=%lld) < d=%d", na, (long long)lda, nb,
                         (long long)ldb, d);
     return SRG_OK;
-}
-
-bool vec4_ok(int d, const void* a, int64_t lda, const void* b, int64_t ldb)
-{
-    return d % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned(a, 16) && aligned(b, 16);
 }
 
 }  // namespace
@@ -138,21 +109,19 @@ int srg_gconv_rows_f32(const int64_t* indptr, const int32_t* indices, const floa
     if (!rows || !Y) return srg_fail(SRG_ERR_INVALID, "null rows or Y");
     if (n_rows > 0 && !indptr) return srg_fail(SRG_ERR_INVALID, "null indptr");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool v4 = vec4_ok(d, X, ldx, Y, ldy);
+    const bool v4 = rows_aligned(4, sizeof(float), d, {{X, ldx}, {Y, ldy}});
     const int tile = v4 ? 256 : 64;
     const unsigned tiles = (unsigned)((d + tile - 1) / tile);
-    const int64_t blocks = (B + kWavesPerBlock - 1) / kWavesPerBlock, per_launch = kMaxLaunchBlocks;
-    for (int64_t b0 = 0; b0 < blocks; b0 += per_launch) {
-        const dim3 grid((unsigned)std::min<int64_t>(per_launch, blocks - b0), tiles);
+    rc = launch_chunks((B + kWavesPerBlock - 1) / kWavesPerBlock, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (v4)
-            hipLaunchKernelGGL(k_gconv_rows<4>, grid, dim3(kBlock), 0, s, indptr, indices, values, n_rows, rows, B, X,
-                               ldx, Y, ldy, d, (int)b0);
+            hipLaunchKernelGGL(k_gconv_rows<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr, indices, values, n_rows,
+                               rows, B, X, ldx, Y, ldy, d, (int)b0);
         else
-            hipLaunchKernelGGL(k_gconv_rows<1>, grid, dim3(kBlock), 0, s, indptr, indices, values, n_rows, rows, B, X,
-                               ldx, Y, ldy, d, (int)b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+            hipLaunchKernelGGL(k_gconv_rows<1>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr, indices, values, n_rows,
+                               rows, B, X, ldx, Y, ldy, d, (int)b0);
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 int srg_gconv_rows_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t, const float* values_t, int64_t n,
@@ -166,21 +135,19 @@ int srg_gconv_rows_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t
     if (!indptr_t || !pos || !dX) return srg_fail(SRG_ERR_INVALID, "null indptr_t, pos or dX");
     if (B > 0 && !G) return srg_fail(SRG_ERR_INVALID, "null G with B=%lld", (long long)B);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool v4 = vec4_ok(d, G, ldg, dX, ldx);
+    const bool v4 = rows_aligned(4, sizeof(float), d, {{G, ldg}, {dX, ldx}});
     const int tile = v4 ? 256 : 64;
     const unsigned tiles = (unsigned)((d + tile - 1) / tile);
-    const int64_t blocks = (n + kWavesPerBlock - 1) / kWavesPerBlock, per_launch = kMaxLaunchBlocks;
-    for (int64_t b0 = 0; b0 < blocks; b0 += per_launch) {
-        const dim3 grid((unsigned)std::min<int64_t>(per_launch, blocks - b0), tiles);
+    rc = launch_chunks((n + kWavesPerBlock - 1) / kWavesPerBlock, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (v4)
-            hipLaunchKernelGGL(k_gconv_rows_adjoint<4>, grid, dim3(kBlock), 0, s, indptr_t, indices_t, values_t, n, pos,
-                               B, G, ldg, dX, ldx, d, (int)b0);
+            hipLaunchKernelGGL(k_gconv_rows_adjoint<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr_t, indices_t,
+                               values_t, n, pos, B, G, ldg, dX, ldx, d, (int)b0);
         else
-            hipLaunchKernelGGL(k_gconv_rows_adjoint<1>, grid, dim3(kBlock), 0, s, indptr_t, indices_t, values_t, n, pos,
-                               B, G, ldg, dX, ldx, d, (int)b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+            hipLaunchKernelGGL(k_gconv_rows_adjoint<1>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr_t, indices_t,
+                               values_t, n, pos, B, G, ldg, dX, ldx, d, (int)b0);
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 }  // extern "C"

@@ -695,10 +695,9 @@ int hop_shape(const float* const* panels, const int64_t* ldp, int T, int start, 
         if (!wide[e]) return srg_fail(SRG_ERR_INVALID, "null pointer");
     hs.vec = 1;
     for (int v = 4; v > 1 && hs.vec == 1; v >>= 1) {
-        const size_t a = v * sizeof(float);
-        bool ok = d % v == 0;
-        for (int t = 0; ok && t < T; ++t) ok = ldp[t] % v == 0 && aligned(panels[t], a);
-        for (int e = 0; ok && e < n_wide; ++e) ok = wide_ld[e] % v == 0 && aligned(wide[e], a);
+        bool ok = true;
+        for (int t = 0; ok && t < T; ++t) ok = rows_aligned(v, sizeof(float), d, {{panels[t], ldp[t]}});
+        for (int e = 0; ok && e < n_wide; ++e) ok = rows_aligned(v, sizeof(float), d, {{wide[e], wide_ld[e]}});
         if (ok) hs.vec = v;
     }
     hs.cpr = d / hs.vec;

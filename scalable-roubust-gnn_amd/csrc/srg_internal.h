@@ -1,12 +1,14 @@
 // srg_internal.h -- host plumbing shared by every translation unit of the library: the thread-local
-// status behind srg_last_error, the HIP status check, the device guard of the entry points and the fork
-// of hub work onto a side stream.  Defined once, in srg_runtime.hip.  Not part of the C-ABI
-// (include/srgnn_hip.h).
+// status behind srg_last_error, the HIP status check, the walk of a grid in launch-sized chunks, the device
+// guard of the entry points and the fork of hub work onto a side stream.  Defined once, in srg_runtime.hip
+// (the chunk walk here).  Not part of the C-ABI (include/srgnn_hip.h).
 #ifndef SRG_INTERNAL_H_
 #define SRG_INTERNAL_H_
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdint>
 #include <mutex>
 
 #include "srgnn_hip.h"
@@ -24,6 +26,31 @@ int srg_ok();
         if (e_ != hipSuccess)                                                                   \
             return srg_fail(SRG_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
     } while (0)
+
+// SRG_HIP_CHECK(hipGetLastError()) as a function: what a callable of launch_chunks returns after its launch.
+inline int launch_status()
+{
+    SRG_HIP_CHECK(hipGetLastError());
+    return SRG_OK;
+}
+
+// A dispatch holds < 2^32 work-items per dimension: launches of more rows than that (111 M rows of the
+// papers100M-shaped graph = 7.1e9 lanes) go out in chunks, the kernel adding the chunk's block_base to
+// blockIdx.x or being handed pointers shifted by the chunk.  Both caps are the same 2^31-lane bound:
+// 2^23 blocks of 256 lanes, 2^24 blocks of one 64-lane wave.
+constexpr int64_t kMaxLaunchBlocks = int64_t(1) << 23;
+constexpr int64_t kMaxLaunchWaveBlocks = int64_t(1) << 24;
+
+// Walks [0, blocks) in ascending chunks of at most per_launch blocks: launch(b0, nb) launches blocks
+// [b0, b0 + nb) and returns its status (launch_status()); the first non-zero status ends the walk and is
+// returned.  Calls no HIP API itself.
+template <typename Launch>
+int launch_chunks(int64_t blocks, int64_t per_launch, Launch launch)
+{
+    for (int64_t b0 = 0; b0 < blocks; b0 += per_launch)
+        if (int rc = launch(b0, (unsigned)std::min<int64_t>(per_launch, blocks - b0))) return rc;
+    return SRG_OK;
+}
 
 // Makes the device of `s` current for the lifetime of the guard (the null stream means the
 // current device), so every launch, event and side stream of an entry point belongs to the

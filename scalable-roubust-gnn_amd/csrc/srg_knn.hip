@@ -313,11 +313,10 @@ int srg_knn_select_f32(const float* X, int64_t ldx, int64_t n, int32_t d, const 
     int wpb = kWavesPerBlock;
     while (wpb > 1 && wpb * per_wave > 65536) wpb /= 2;
     const size_t lds = wpb * per_wave;
-    const bool v4 = ldx % 4 == 0 && aligned(X, 16);
+    const bool v4 = rows_aligned(4, sizeof(float), 0, {{X, ldx}});   // whatever d is: a row's tail is read by the element
     const int G = group_lanes(d);
-    const int64_t blocks = (n_query + wpb - 1) / wpb, per_launch = SRG_KNN_LAUNCH_ROWS / wpb;
-    for (int64_t b0 = 0; b0 < blocks; b0 += per_launch) {
-        const dim3 grid((unsigned)std::min<int64_t>(per_launch, blocks - b0)), block(64 * wpb);
+    rc = launch_chunks((n_query + wpb - 1) / wpb, SRG_KNN_LAUNCH_ROWS / wpb, [&](int64_t b0, unsigned nb) {
+        const dim3 grid(nb), block(64 * wpb);
 #define SRG_KNN_CASE(GG)                                                                                        \
     case GG:                                                                                                    \
         launch_select<GG>(v4, grid, block, lds, s, X, ldx, n, d, query, cand_ptr, cand, out_ptr, n_query, sel,   \
@@ -334,9 +333,9 @@ int srg_knn_select_f32(const float* X, int64_t ldx, int64_t n, int32_t d, const 
             SRG_KNN_CASE(64);
         }
 #undef SRG_KNN_CASE
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 int srg_sample_distinct_i64(const int64_t* query, const int64_t* cand_ptr, int64_t n_query, int64_t n,
@@ -361,13 +360,11 @@ int srg_sample_distinct_i64(const int64_t* query, const int64_t* cand_ptr, int64
     int h = 1;
     while ((uint64_t(1) << (2 * h)) < (uint64_t)(n - 1)) ++h;
     const int64_t blocks = (n_query + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t per_launch = SRG_KNN_LAUNCH_ROWS / kWavesPerBlock;
-    for (int64_t b0 = 0; b0 < blocks; b0 += per_launch) {
-        const dim3 grid((unsigned)std::min<int64_t>(per_launch, blocks - b0));
-        hipLaunchKernelGGL(k_sample_distinct, grid, dim3(kBlock), 0, s, query, cand_ptr, n_query, n, seed, h, cand, b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+    rc = launch_chunks(blocks, SRG_KNN_LAUNCH_ROWS / kWavesPerBlock, [&](int64_t b0, unsigned nb) {
+        hipLaunchKernelGGL(k_sample_distinct, dim3(nb), dim3(kBlock), 0, s, query, cand_ptr, n_query, n, seed, h, cand, b0);
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 }  // extern "C"

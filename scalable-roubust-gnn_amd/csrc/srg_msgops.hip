@@ -328,12 +328,10 @@ int srg_hop_simweight_f32(const float* x0, int64_t ldx0, const float* y, int64_t
     // the widest access every row of every panel is aligned for (pick_vec's d thresholds are the
     // SpMM's tile widths; a streaming pass takes 16 bytes per lane from d = 4)
     int vec = 1;
-    for (int v = 4; v > 1 && vec == 1; v >>= 1) {
-        const size_t a = v * sizeof(float);
-        if (d % v == 0 && ldy % v == 0 && lda % v == 0 && aligned(y, a) && aligned(acc, a) &&
-            (hop0 || (ldx0 % v == 0 && aligned(x0, a))))
+    for (int v = 4; v > 1 && vec == 1; v >>= 1)   // x0 is not read at hop 0
+        if (rows_aligned(v, sizeof(float), d, {{y, ldy}, {acc, lda}}) &&
+            (hop0 || rows_aligned(v, sizeof(float), d, {{x0, ldx0}})))
             vec = v;
-    }
     const int cpr = d / vec;
     int lgS = 0;
     while (lgS < 6 && (1 << lgS) < cpr) ++lgS;

@@ -4,7 +4,6 @@
 // owner wave (or lane group), so the results are the same bits run after run.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
 
 #include "srgnn_hip.h"
@@ -206,17 +205,17 @@ int srg_dense_sparsify_f64(int phase, const double* R, int64_t ldr, int64_t n_ro
     if (!R || (phase == 0 ? !cnt : !ptr)) return srg_fail(SRG_ERR_INVALID, "null R, cnt (phase 0) or ptr (phase 1)");
     hipStream_t s = static_cast<hipStream_t>(stream);
     // 16-byte loads where every row starts on 16 bytes; else 8-byte loads, the same bits
-    const bool vec2 = ldr % 2 == 0 && aligned(R, 16);
+    // (whatever w is: the kernel takes a row's odd last column by itself)
+    const bool vec2 = rows_aligned(2, sizeof(double), 0, {{R, ldr}});
     const int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxLaunchBlocks) {
-        const dim3 grid((unsigned)std::min<int64_t>(kMaxLaunchBlocks, blocks - b0));
+    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (vec2)
-            launch_sparsify<2>(phase, grid, s, R, ldr, n_rows, w, tolerance, col0, cnt, ptr, idx, val, b0);
+            launch_sparsify<2>(phase, dim3(nb), s, R, ldr, n_rows, w, tolerance, col0, cnt, ptr, idx, val, b0);
         else
-            launch_sparsify<1>(phase, grid, s, R, ldr, n_rows, w, tolerance, col0, cnt, ptr, idx, val, b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+            launch_sparsify<1>(phase, dim3(nb), s, R, ldr, n_rows, w, tolerance, col0, cnt, ptr, idx, val, b0);
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 int srg_csr_append_rows_f32(const int64_t* src_ptr, const int32_t* src_idx, const float* src_val, int64_t n_rows,
@@ -228,13 +227,12 @@ int srg_csr_append_rows_f32(const int64_t* src_ptr, const int32_t* src_idx, cons
     if (!src_ptr || !cursor) return srg_fail(SRG_ERR_INVALID, "null src_ptr or cursor");
     const int64_t rows_per_block = 4 * kWavesPerBlock;
     const int64_t blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxLaunchBlocks) {
-        const dim3 grid((unsigned)std::min<int64_t>(kMaxLaunchBlocks, blocks - b0));
-        hipLaunchKernelGGL(k_csr_append_rows, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), src_ptr,
+    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+        hipLaunchKernelGGL(k_csr_append_rows, dim3(nb), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src_ptr,
                            src_idx, src_val, n_rows, cursor, dst_idx, dst_val, b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 int srg_csr_row_normalize_l1_f32(const int64_t* indptr, float* values, int64_t n_rows, void* stream)
@@ -245,13 +243,12 @@ int srg_csr_row_normalize_l1_f32(const int64_t* indptr, float* values, int64_t n
     if (!indptr) return srg_fail(SRG_ERR_INVALID, "null indptr");
     const int64_t rows_per_block = 64 * kWavesPerBlock;
     const int64_t blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxLaunchBlocks) {
-        const dim3 grid((unsigned)std::min<int64_t>(kMaxLaunchBlocks, blocks - b0));
-        hipLaunchKernelGGL(k_csr_row_normalize_l1, grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), indptr,
+    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+        hipLaunchKernelGGL(k_csr_row_normalize_l1, dim3(nb), dim3(kBlock), 0, static_cast<hipStream_t>(stream), indptr,
                            values, n_rows, b0);
-        SRG_HIP_CHECK(hipGetLastError());
-    }
-    return srg_ok();
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 }  // extern "C"

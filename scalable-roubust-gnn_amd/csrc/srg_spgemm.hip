@@ -31,6 +31,7 @@
 #include <cstdio>
 #include <type_traits>
 
+#include "srg_device.h"
 #include "srg_internal.h"
 #include "srgnn_hip.h"
 
@@ -404,15 +405,13 @@ int srg_spmm_muladd_f32(const int64_t* indptr, const int32_t* indices, const flo
     if (n_rows == 0 || d == 0) return srg_ok();
     if (!indptr || !Y) return srg_fail(SRG_ERR_INVALID, "null pointer");
     SRG_DEVICE_GUARD(stream);
-    const int64_t blocks = (n_rows + 3) / 4;
-    for (int64_t b0 = 0; b0 < blocks; b0 += (int64_t)1 << 23) {     // < 2^31 work-items per launch
-        const int64_t nb = blocks - b0 < ((int64_t)1 << 23) ? blocks - b0 : ((int64_t)1 << 23);
+    const int rc = launch_chunks((n_rows + 3) / 4, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         const int64_t r0 = b0 * 4;
-        hipLaunchKernelGGL(k_spmm_muladd, dim3((unsigned)nb), dim3(256), 0, static_cast<hipStream_t>(stream),
+        hipLaunchKernelGGL(k_spmm_muladd, dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream),
                            indptr + r0, indices, values, n_rows - r0, X, ldx, Y + r0 * ldy, ldy, d);
-    }
-    SRG_HIP_CHECK(hipGetLastError());
-    return srg_ok();
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 int srg_sddmm_f32(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const float* G,
@@ -428,20 +427,18 @@ int srg_sddmm_f32(const int64_t* indptr, const int32_t* indices, int64_t n_rows,
     if (n_rows == 0 || nnz == 0) return srg_ok();
     if (!out || (d > 0 && (!indptr || !indices || !G || !X))) return srg_fail(SRG_ERR_INVALID, "null pointer");
     SRG_DEVICE_GUARD(stream);
-    const bool vec = ((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(X)) & 15) == 0 &&
-                     ldg % 4 == 0 && ldx % 4 == 0;
-    const int64_t blocks = (nnz + kWave - 1) / kWave;
-    for (int64_t b0 = 0; b0 < blocks; b0 += (int64_t)1 << 24) {     // < 2^31 work-items per launch
-        const int64_t nb = blocks - b0 < ((int64_t)1 << 24) ? blocks - b0 : ((int64_t)1 << 24);
+    // (whatever d is: the kernel takes a row's last d % 4 columns by the element)
+    const bool vec = rows_aligned(4, sizeof(float), 0, {{G, ldg}, {X, ldx}});
+    const int rc = launch_chunks((nnz + kWave - 1) / kWave, kMaxLaunchWaveBlocks, [&](int64_t b0, unsigned nb) {
         if (vec)
-            hipLaunchKernelGGL(k_sddmm<true>, dim3((unsigned)nb), dim3(kWave), 0, static_cast<hipStream_t>(stream),
+            hipLaunchKernelGGL(k_sddmm<true>, dim3(nb), dim3(kWave), 0, static_cast<hipStream_t>(stream),
                                indptr, indices, n_rows, b0 * kWave, nnz, G, ldg, X, ldx, d, perm, out);
         else
-            hipLaunchKernelGGL(k_sddmm<false>, dim3((unsigned)nb), dim3(kWave), 0, static_cast<hipStream_t>(stream),
+            hipLaunchKernelGGL(k_sddmm<false>, dim3(nb), dim3(kWave), 0, static_cast<hipStream_t>(stream),
                                indptr, indices, n_rows, b0 * kWave, nnz, G, ldg, X, ldx, d, perm, out);
-    }
-    SRG_HIP_CHECK(hipGetLastError());
-    return srg_ok();
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 }  // extern "C"

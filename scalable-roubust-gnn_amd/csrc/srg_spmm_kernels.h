@@ -1051,8 +1051,8 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
     const int nr = (int)m_rows, nh = (int)n_heavy;
     const int pu = (flags & SRG_SPMM_PACKED_U2) ? 2 : kPackedU;
     const unsigned shm = (unsigned)spmm_lds_bytes(flags);
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxLaunchBlocks) {
-        const dim3 grid((unsigned)std::min<int64_t>(kMaxLaunchBlocks, blocks - b0));
+    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+        const dim3 grid(nb);
         const int bb = (int)b0;
 #define SRG_LAUNCH_SPMM(V, F, SF)                                                               \
     hipLaunchKernelGGL((k_spmm<V, kUnroll, kUnrollHeavy, F, SF, IP, 0, EX>), grid, dim3(kBlock), shm, s,   \
@@ -1116,8 +1116,9 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
 #undef SRG_LAUNCH_NARROW
 #undef SRG_LAUNCH_PACKED
 #undef SRG_LAUNCH_PACKED_U
-        SRG_HIP_CHECK(hipGetLastError());
-    }
+        return launch_status();
+    });
+    if (rc) return rc;
     return nojoin ? SRG_OK : hub.join();
 }
 

@@ -178,18 +178,17 @@ __global__ __launch_bounds__(kWave) void k_sddmm_rowsum(const int64_t* __restric
 }
 
 template <int W>
-void launch_scaled(int64_t n_rows, hipStream_t s, const int64_t* ip, const int32_t* ix, const float* vv,
-                   const float* scale, int axis, const float* X, int64_t ldx, float* Y, int64_t ldy, int d)
+int launch_scaled(int64_t n_rows, hipStream_t s, const int64_t* ip, const int32_t* ix, const float* vv,
+                  const float* scale, int axis, const float* X, int64_t ldx, float* Y, int64_t ldy, int d)
 {
     constexpr int kRows = 4 * (kWave / W);                  // rows per 256-lane workgroup
-    const int64_t blocks = (n_rows + kRows - 1) / kRows;
-    for (int64_t b0 = 0; b0 < blocks; b0 += (int64_t)1 << 23) {     // < 2^31 work-items per launch
-        const int64_t nb = blocks - b0 < ((int64_t)1 << 23) ? blocks - b0 : ((int64_t)1 << 23);
+    return launch_chunks((n_rows + kRows - 1) / kRows, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         const int64_t r0 = b0 * kRows;
-        hipLaunchKernelGGL(k_spmm_scaled<W>, dim3((unsigned)nb), dim3(256), 0, s, ip + r0, ix, vv,
+        hipLaunchKernelGGL(k_spmm_scaled<W>, dim3(nb), dim3(256), 0, s, ip + r0, ix, vv,
                            (scale && axis == 1) ? scale + r0 : scale, axis, n_rows - r0, X, ldx, Y + r0 * ldy, ldy,
                            d);
-    }
+        return launch_status();
+    });
 }
 
 }  // namespace
@@ -210,16 +209,16 @@ int srg_spmm_scaled_f32(const int64_t* indptr, const int32_t* indices, const flo
     SRG_DEVICE_GUARD(stream);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define SRG_SCALED(W) launch_scaled<W>(n_rows, s, indptr, indices, values, scale, scale_axis, X, ldx, Y, ldy, d)
-    if (d <= 1) SRG_SCALED(1);
-    else if (d <= 2) SRG_SCALED(2);
-    else if (d <= 4) SRG_SCALED(4);
-    else if (d <= 8) SRG_SCALED(8);
-    else if (d <= 16) SRG_SCALED(16);
-    else if (d <= 32) SRG_SCALED(32);
-    else SRG_SCALED(64);
+    int rc;
+    if (d <= 1) rc = SRG_SCALED(1);
+    else if (d <= 2) rc = SRG_SCALED(2);
+    else if (d <= 4) rc = SRG_SCALED(4);
+    else if (d <= 8) rc = SRG_SCALED(8);
+    else if (d <= 16) rc = SRG_SCALED(16);
+    else if (d <= 32) rc = SRG_SCALED(32);
+    else rc = SRG_SCALED(64);
 #undef SRG_SCALED
-    SRG_HIP_CHECK(hipGetLastError());
-    return srg_ok();
+    return rc ? rc : srg_ok();
 }
 
 int srg_sddmm_rowsum_f32(const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows,
@@ -238,13 +237,12 @@ int srg_sddmm_rowsum_f32(const int64_t* indptr, const int32_t* indices, const fl
         SRG_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n_rows * sizeof(float), s));
         return srg_ok();
     }
-    for (int64_t r0 = 0; r0 < n_rows; r0 += (int64_t)1 << 24) {     // < 2^31 work-items per launch
-        const int64_t nb = n_rows - r0 < ((int64_t)1 << 24) ? n_rows - r0 : ((int64_t)1 << 24);
-        hipLaunchKernelGGL(k_sddmm_rowsum, dim3((unsigned)nb), dim3(kWave), 0, s, indptr + r0, indices, values, G,
-                           ldg, P + r0 * ldp, ldp, d, out + r0);
-    }
-    SRG_HIP_CHECK(hipGetLastError());
-    return srg_ok();
+    const int rc = launch_chunks(n_rows, kMaxLaunchWaveBlocks, [&](int64_t r0, unsigned nb) {   // a row per block
+        hipLaunchKernelGGL(k_sddmm_rowsum, dim3(nb), dim3(kWave), 0, s, indptr + r0, indices, values, G, ldg,
+                           P + r0 * ldp, ldp, d, out + r0);
+        return launch_status();
+    });
+    return rc ? rc : srg_ok();
 }
 
 }  // extern "C"
