@@ -1103,6 +1103,18 @@ int srg_last_error_code(void);      /* thread-local status of the last call (SRG
 void srg_clear_error(void);
 const char* srg_version(void);      /* build identification, incl. the offload arch          */
 
+/* ---- test hooks ------------------------------------------------------------------------------ */
+/* Every kernel family sends a large grid out in several launches (of at most 2^23 blocks, 2^24 one-wave
+ * blocks, or SRG_GAT_LAUNCH_ROWS / SRG_KNN_LAUNCH_ROWS rows), and the grid-stride kernels clip their
+ * grids.  srg_debug_launch_cap sets a process-wide upper bound on the blocks of ONE launch, so that
+ * tests cross those chunk boundaries and stride trips at a few thousand rows; it returns the previous
+ * bound (0: none), and blocks <= 0 removes the bound.  A bound above a site's own cap changes nothing
+ * there.  It changes scheduling only, never results; it is read once per entry call, so set it while
+ * no other thread is inside the library.  Not for production use. */
+int64_t srg_debug_launch_cap(int64_t blocks);
+/* The number of kernel launches issued through the chunk walk so far: monotonic, process-wide. */
+int64_t srg_debug_chunk_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -458,7 +458,7 @@ int launch_cheby(const int64_t* indptr, const int32_t* indices, const T* vals, i
                         ? 2
                         : 1;
     const int nr = (int)n_rows;
-    rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (vec == 2)
             hipLaunchKernelGGL((k_cheby<T, 2, kUnroll>), dim3(nb), dim3(kBlock), 0, s, indptr, indices,
                                vals, order, nr, Tc, To, Tn, ld, d, mode, a1, a2, cf, n_scales, R,
@@ -597,7 +597,7 @@ __attribute__((visibility("hidden"))) int srg_run_plan_cheby_f64(const srg_hop_l
         const int64_t blocks = (L.n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
         const int nr = (int)L.n_rows;
         // (uncapped: 4 or 6 waves per SIMD measured 0.5-3 % slower, profiles/r06i_cheby64_plan_sweep.txt)
-        const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+        const int rc = launch_chunks_capped(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
 #define SRG_LAUNCH_BLK64(V, F, LA)                                                                                \
     hipLaunchKernelGGL((k_cheby_blk64<V, kUnroll, F, LA>), dim3(nb), dim3(kBlock), 0, s, L.slot_beg, L.slot_end, \
                        L.row_order, nr, indices, values, Tc, To, Tn, ld, d, mode, a1, a2, cf, n_scales, R, r_stride, \
@@ -655,7 +655,7 @@ int srg_cheby_epilogue_f32(float* Tn, int64_t ldn, const float* Tc, int64_t ldc,
     if (n_rows == 0 || d == 0) return srg_ok();
     if (!Tn || (needs_r && !R) || (init ? !Tc : !To) || (m == SRG_CHEBY_STEP_FIRST && !Tc))
         return srg_fail(SRG_ERR_INVALID, "null panel");
-    const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 256 * 16);
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + 3) / 4, launch_cap(256 * 16));
     hipLaunchKernelGGL(k_cheby_epilogue, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        Tn, ldn, Tc, ldc, To, ldo, n_rows, d, mode, a1, a2, cf, n_scales, R, ldr, r_stride);
     SRG_HIP_CHECK(hipGetLastError());

@@ -426,7 +426,7 @@ int srg_dist_propagate_khop_f32(srg_comm* comm, const srg_shard_f32* shards, int
         hipError_t e = hipMemcpyAsync(bounds, row_starts, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, st(i));
         if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4, st(i));
         if (e == hipSuccess && s.n_rows > 0) {
-            const unsigned grid = (unsigned)std::min<int64_t>((s.n_rows * 64 + 255) / 256, 1 << 20);
+            const unsigned grid = (unsigned)std::min<int64_t>((s.n_rows * 64 + 255) / 256, launch_cap(1 << 20));
             hipLaunchKernelGGL(k_owner_splits, dim3(grid), dim3(256), 0, st(i), s.indptr, s.indices, s.n_rows, bounds,
                                P, splits[i], bad);
             e = hipGetLastError();

@@ -301,7 +301,7 @@ int launch_segment_sum(const int64_t* seg_ptr, const T* vals, int64_t n_seg, T* 
     if (n_seg < 0) return srg_fail(SRG_ERR_INVALID, "n_seg=%lld < 0", (long long)n_seg);
     if (n_seg == 0) return srg_ok();
     if (!seg_ptr || !out) return srg_fail(SRG_ERR_INVALID, "null pointer");
-    const unsigned blocks = (unsigned)std::min<int64_t>((n_seg + 255) / 256, 1 << 16);   // 64 segments per wave
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_seg + 255) / 256, launch_cap(1 << 16));   // 64 segments per wave
     hipLaunchKernelGGL(k_segment_sum<T>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        seg_ptr, vals, n_seg, out);
     SRG_HIP_CHECK(hipGetLastError());
@@ -328,7 +328,7 @@ int srg_segment_sum_numpy_f64(const int64_t* seg_ptr, const double* vals, int64_
     if (n_seg < 0) return srg_fail(SRG_ERR_INVALID, "n_seg=%lld < 0", (long long)n_seg);
     if (n_seg == 0) return srg_ok();
     if (!seg_ptr || !out) return srg_fail(SRG_ERR_INVALID, "null pointer");
-    const unsigned blocks = (unsigned)std::min<int64_t>((n_seg + 255) / 256, 1 << 16);   // 64 segments per wave
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_seg + 255) / 256, launch_cap(1 << 16));   // 64 segments per wave
     hipLaunchKernelGGL(k_segment_sum_numpy, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        seg_ptr, vals, n_seg, out);
     SRG_HIP_CHECK(hipGetLastError());
@@ -343,7 +343,7 @@ int srg_spmm_csr_f64(const int64_t* indptr, const int32_t* indices, const double
     if (rc) return rc;
     if (n_rows == 0 || d == 0) return srg_ok();
     const int64_t total = n_rows * (int64_t)d;
-    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20);
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, launch_cap(1 << 20));
     hipLaunchKernelGGL(k_spmm_f64, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        indptr, indices, values, n_rows, X, ldx, Y, ldy, d);
     SRG_HIP_CHECK(hipGetLastError());
@@ -362,7 +362,7 @@ int srg_csr_validate(const int64_t* indptr, const int32_t* indices, int64_t n_ro
     SRG_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&d_bad), sizeof(unsigned int), s));
     SRG_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned int), s));
     const int64_t work = std::max(nnz, n_rows);
-    const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((work + 255) / 256, 1), 8192);
+    const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((work + 255) / 256, 1), launch_cap(8192));
     hipLaunchKernelGGL(k_validate, dim3(blocks), dim3(256), 0, s, indptr, indices, n_rows, nnz, n_cols, d_bad);
     SRG_HIP_CHECK(hipGetLastError());
     unsigned int bad = 0;
@@ -402,7 +402,7 @@ int srg_csr_copy_spans(const int32_t* order, int64_t n_order, const int64_t* beg
     if (!order || !beg || !end || !pos || !out_beg || !out_end)
         return srg_fail(SRG_ERR_INVALID, "null order / span / position array");
     const int64_t rows_per_block = 256 / 16;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n_order + rows_per_block - 1) / rows_per_block, 1 << 20);
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_order + rows_per_block - 1) / rows_per_block, launch_cap(1 << 20));
     hipLaunchKernelGGL(k_copy_spans, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), order, n_order,
                        beg, end, indices, values, pos, out_indices, out_values, out_beg, out_end);
     SRG_HIP_CHECK(hipGetLastError());
@@ -416,7 +416,7 @@ int srg_csr_mirror(const int64_t* indptr, const int32_t* indices, const int64_t*
     if (n_rows < 0 || nnz < 0) return srg_fail(SRG_ERR_INVALID, "negative size");
     if (nnz == 0) return srg_ok();
     if (!indptr || !indices || !rows || !mirror) return srg_fail(SRG_ERR_INVALID, "null pointer");
-    const unsigned blocks = (unsigned)std::min<int64_t>((nnz + 255) / 256, 1 << 20);
+    const unsigned blocks = (unsigned)std::min<int64_t>((nnz + 255) / 256, launch_cap(1 << 20));
     hipLaunchKernelGGL(k_csr_mirror, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), indptr, indices,
                        rows, nnz, mirror);
     SRG_HIP_CHECK(hipGetLastError());

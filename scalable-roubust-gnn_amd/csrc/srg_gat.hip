@@ -332,13 +332,13 @@ int srg_gat_attend_f32(const int64_t* indptr, const int32_t* indices, int64_t nn
     const int tile = v4 ? 256 : 64;
     const unsigned tiles = (unsigned)((W + tile - 1) / tile);
     const int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         hipLaunchKernelGGL(k_gat_stats, dim3(nb), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src, a_src, a_dst,
                            slope, (int)H, M, Z, (int)b0);
         return launch_status();
     });
     if (rc) return rc;
-    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         if (v4)
             hipLaunchKernelGGL(k_gat_attend<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src,
                                a_src, a_dst, slope, Hf, ldh, (int)H, (int)C, M, Z, out, ldo, (int)b0);
@@ -371,7 +371,7 @@ int srg_gat_edge_grad_f32(const int64_t* indptr, const int32_t* indices, int64_t
         return srg_fail(SRG_ERR_INVALID, "null operand");
     const int64_t total = n_rows * H;   // one thread per item: kRowsPerLaunch items are whole blocks
     const bool v4d = rows_aligned(4, sizeof(float), C, {{G, ldg}, {out, ldo}});
-    rc = launch_chunks((total + kBlock - 1) / kBlock, kRowsPerLaunch / kBlock, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped((total + kBlock - 1) / kBlock, kRowsPerLaunch / kBlock, [&](int64_t b0, unsigned nb) {
         if (v4d)
             hipLaunchKernelGGL(k_gat_rowdot<true>, dim3(nb), dim3(kBlock), 0, s, total, (int)H, (int)C, G, ldg, out, ldo,
                                D, b0 * kBlock);
@@ -383,7 +383,7 @@ int srg_gat_edge_grad_f32(const int64_t* indptr, const int32_t* indices, int64_t
     if (rc) return rc;
     const bool v4e = rows_aligned(4, sizeof(float), C, {{G, ldg}, {Hf, ldh}});
     const int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         if (v4e)
             hipLaunchKernelGGL(k_gat_edge<true>, dim3(nb), dim3(kBlock), 0, s, indptr, indices, n_rows, n_src, nnz, a_src,
                                a_dst, slope, Hf, ldh, (int)H, (int)C, M, Z, G, ldg, D, dS, (int)b0);
@@ -393,7 +393,7 @@ int srg_gat_edge_grad_f32(const int64_t* indptr, const int32_t* indices, int64_t
         return launch_status();
     });
     if (rc) return rc;
-    rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
         hipLaunchKernelGGL(k_gat_rowsum, dim3(nb), dim3(kBlock), 0, s, indptr, (const int64_t*)nullptr, n_rows, nnz,
                            (int)H, dS, da_dst, (int)b0);
         return launch_status();
@@ -427,7 +427,7 @@ int srg_gat_attend_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t
         const bool v4 = rows_aligned(4, sizeof(float), C, {{G, ldg}, {dHf, ldd}});
         const int tile = v4 ? 256 : 64;
         const unsigned tiles = (unsigned)((W + tile - 1) / tile);
-        rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
+        rc = launch_chunks_capped(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
             if (v4)
                 hipLaunchKernelGGL(k_gat_adjoint<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr_t, indices_t, n_rows,
                                    n_src, a_src, a_dst, slope, (int)H, (int)C, M, Z, G, ldg, dHf, ldd, (int)b0);
@@ -439,7 +439,7 @@ int srg_gat_attend_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t
         if (rc) return rc;
     }
     if (da_src)
-        rc = launch_chunks(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
+        rc = launch_chunks_capped(blocks, kBlocksPerLaunch, [&](int64_t b0, unsigned nb) {
             hipLaunchKernelGGL(k_gat_rowsum, dim3(nb), dim3(kBlock), 0, s, indptr_t, perm, n_src, nnz, (int)H, dS, da_src,
                                (int)b0);
             return launch_status();

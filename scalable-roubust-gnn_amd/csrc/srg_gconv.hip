@@ -112,7 +112,7 @@ int srg_gconv_rows_f32(const int64_t* indptr, const int32_t* indices, const floa
     const bool v4 = rows_aligned(4, sizeof(float), d, {{X, ldx}, {Y, ldy}});
     const int tile = v4 ? 256 : 64;
     const unsigned tiles = (unsigned)((d + tile - 1) / tile);
-    rc = launch_chunks((B + kWavesPerBlock - 1) / kWavesPerBlock, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped((B + kWavesPerBlock - 1) / kWavesPerBlock, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (v4)
             hipLaunchKernelGGL(k_gconv_rows<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr, indices, values, n_rows,
                                rows, B, X, ldx, Y, ldy, d, (int)b0);
@@ -138,7 +138,7 @@ int srg_gconv_rows_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t
     const bool v4 = rows_aligned(4, sizeof(float), d, {{G, ldg}, {dX, ldx}});
     const int tile = v4 ? 256 : 64;
     const unsigned tiles = (unsigned)((d + tile - 1) / tile);
-    rc = launch_chunks((n + kWavesPerBlock - 1) / kWavesPerBlock, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped((n + kWavesPerBlock - 1) / kWavesPerBlock, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (v4)
             hipLaunchKernelGGL(k_gconv_rows_adjoint<4>, dim3(nb, tiles), dim3(kBlock), 0, s, indptr_t, indices_t,
                                values_t, n, pos, B, G, ldg, dX, ldx, d, (int)b0);

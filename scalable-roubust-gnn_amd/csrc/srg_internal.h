@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <mutex>
 
@@ -50,6 +51,30 @@ int launch_chunks(int64_t blocks, int64_t per_launch, Launch launch)
     for (int64_t b0 = 0; b0 < blocks; b0 += per_launch)
         if (int rc = launch(b0, (unsigned)std::min<int64_t>(per_launch, blocks - b0))) return rc;
     return SRG_OK;
+}
+
+// The test seam behind srg_debug_launch_cap / srg_debug_chunk_launches (include/srgnn_hip.h): a process-wide
+// bound on the blocks of one launch (0: none) and a count of the launches the capped walk has issued.
+// Header-inline, so every translation unit, and the stand-alone host program of the tests, shares one of each.
+inline std::atomic<int64_t> g_launch_cap_override{0};
+inline std::atomic<int64_t> g_chunk_launches{0};
+
+// The blocks of one launch at a site whose own cap is dflt: min(dflt, override) under an override (never
+// below one block), dflt without one.  One relaxed load.
+inline int64_t launch_cap(int64_t dflt)
+{
+    const int64_t o = g_launch_cap_override.load(std::memory_order_relaxed);
+    return o > 0 ? std::max<int64_t>(1, std::min(dflt, o)) : dflt;
+}
+
+// launch_chunks under launch_cap(dflt), counting one chunk launch per call of `launch`.
+template <typename Launch>
+int launch_chunks_capped(int64_t blocks, int64_t dflt, Launch launch)
+{
+    return launch_chunks(blocks, launch_cap(dflt), [&](int64_t b0, unsigned nb) {
+        g_chunk_launches.fetch_add(1, std::memory_order_relaxed);
+        return launch(b0, nb);
+    });
 }
 
 // Makes the device of `s` current for the lifetime of the guard (the null stream means the

@@ -234,7 +234,7 @@ int check_into(unsigned int* d_status, const int64_t* query, const int64_t* cand
                int64_t n_query, int64_t n, int64_t cap, hipStream_t s, unsigned int status[2])
 {
     SRG_HIP_CHECK(hipMemsetAsync(d_status, 0, 2 * sizeof(unsigned int), s));
-    const unsigned blocks = (unsigned)std::min<int64_t>((n_query + 255) / 256, 8192);
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_query + 255) / 256, launch_cap(8192));
     hipLaunchKernelGGL(k_knn_check, dim3(blocks), dim3(256), 0, s, query, cand_ptr, out_ptr, n_query, n, cap,
                        d_status);
     SRG_HIP_CHECK(hipGetLastError());
@@ -315,7 +315,7 @@ int srg_knn_select_f32(const float* X, int64_t ldx, int64_t n, int32_t d, const 
     const size_t lds = wpb * per_wave;
     const bool v4 = rows_aligned(4, sizeof(float), 0, {{X, ldx}});   // whatever d is: a row's tail is read by the element
     const int G = group_lanes(d);
-    rc = launch_chunks((n_query + wpb - 1) / wpb, SRG_KNN_LAUNCH_ROWS / wpb, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped((n_query + wpb - 1) / wpb, SRG_KNN_LAUNCH_ROWS / wpb, [&](int64_t b0, unsigned nb) {
         const dim3 grid(nb), block(64 * wpb);
 #define SRG_KNN_CASE(GG)                                                                                        \
     case GG:                                                                                                    \
@@ -360,7 +360,7 @@ int srg_sample_distinct_i64(const int64_t* query, const int64_t* cand_ptr, int64
     int h = 1;
     while ((uint64_t(1) << (2 * h)) < (uint64_t)(n - 1)) ++h;
     const int64_t blocks = (n_query + kWavesPerBlock - 1) / kWavesPerBlock;
-    rc = launch_chunks(blocks, SRG_KNN_LAUNCH_ROWS / kWavesPerBlock, [&](int64_t b0, unsigned nb) {
+    rc = launch_chunks_capped(blocks, SRG_KNN_LAUNCH_ROWS / kWavesPerBlock, [&](int64_t b0, unsigned nb) {
         hipLaunchKernelGGL(k_sample_distinct, dim3(nb), dim3(kBlock), 0, s, query, cand_ptr, n_query, n, seed, h, cand, b0);
         return launch_status();
     });

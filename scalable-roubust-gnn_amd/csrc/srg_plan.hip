@@ -609,7 +609,7 @@ int bits_for(uint64_t v)
 unsigned grid_for(int64_t work, int per_block, unsigned cap)
 {
     const int64_t g = (work + per_block - 1) / per_block;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(g, cap));
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(g, launch_cap(cap)));
 }
 
 // build temporaries: released after the work enqueued on `s` so far

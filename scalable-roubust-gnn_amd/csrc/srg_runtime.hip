@@ -219,4 +219,11 @@ int srg_last_error_code(void) { return g_err_code; }
 void srg_clear_error(void) { (void)srg_ok(); }
 const char* srg_version(void) { return "srgnn_hip " SRG_GIT_REV " gfx950"; }
 
+int64_t srg_debug_launch_cap(int64_t blocks)
+{
+    return g_launch_cap_override.exchange(blocks > 0 ? blocks : 0, std::memory_order_relaxed);
+}
+
+int64_t srg_debug_chunk_launches(void) { return g_chunk_launches.load(std::memory_order_relaxed); }
+
 }  // extern "C"

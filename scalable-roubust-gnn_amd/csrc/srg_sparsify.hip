@@ -208,7 +208,7 @@ int srg_dense_sparsify_f64(int phase, const double* R, int64_t ldr, int64_t n_ro
     // (whatever w is: the kernel takes a row's odd last column by itself)
     const bool vec2 = rows_aligned(2, sizeof(double), 0, {{R, ldr}});
     const int64_t blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    const int rc = launch_chunks_capped(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         if (vec2)
             launch_sparsify<2>(phase, dim3(nb), s, R, ldr, n_rows, w, tolerance, col0, cnt, ptr, idx, val, b0);
         else
@@ -227,7 +227,7 @@ int srg_csr_append_rows_f32(const int64_t* src_ptr, const int32_t* src_idx, cons
     if (!src_ptr || !cursor) return srg_fail(SRG_ERR_INVALID, "null src_ptr or cursor");
     const int64_t rows_per_block = 4 * kWavesPerBlock;
     const int64_t blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    const int rc = launch_chunks_capped(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         hipLaunchKernelGGL(k_csr_append_rows, dim3(nb), dim3(kBlock), 0, static_cast<hipStream_t>(stream), src_ptr,
                            src_idx, src_val, n_rows, cursor, dst_idx, dst_val, b0);
         return launch_status();
@@ -243,7 +243,7 @@ int srg_csr_row_normalize_l1_f32(const int64_t* indptr, float* values, int64_t n
     if (!indptr) return srg_fail(SRG_ERR_INVALID, "null indptr");
     const int64_t rows_per_block = 64 * kWavesPerBlock;
     const int64_t blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    const int rc = launch_chunks_capped(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         hipLaunchKernelGGL(k_csr_row_normalize_l1, dim3(nb), dim3(kBlock), 0, static_cast<hipStream_t>(stream), indptr,
                            values, n_rows, b0);
         return launch_status();

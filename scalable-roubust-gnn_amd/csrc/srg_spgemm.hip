@@ -405,7 +405,7 @@ int srg_spmm_muladd_f32(const int64_t* indptr, const int32_t* indices, const flo
     if (n_rows == 0 || d == 0) return srg_ok();
     if (!indptr || !Y) return srg_fail(SRG_ERR_INVALID, "null pointer");
     SRG_DEVICE_GUARD(stream);
-    const int rc = launch_chunks((n_rows + 3) / 4, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    const int rc = launch_chunks_capped((n_rows + 3) / 4, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         const int64_t r0 = b0 * 4;
         hipLaunchKernelGGL(k_spmm_muladd, dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream),
                            indptr + r0, indices, values, n_rows - r0, X, ldx, Y + r0 * ldy, ldy, d);
@@ -429,7 +429,7 @@ int srg_sddmm_f32(const int64_t* indptr, const int32_t* indices, int64_t n_rows,
     SRG_DEVICE_GUARD(stream);
     // (whatever d is: the kernel takes a row's last d % 4 columns by the element)
     const bool vec = rows_aligned(4, sizeof(float), 0, {{G, ldg}, {X, ldx}});
-    const int rc = launch_chunks((nnz + kWave - 1) / kWave, kMaxLaunchWaveBlocks, [&](int64_t b0, unsigned nb) {
+    const int rc = launch_chunks_capped((nnz + kWave - 1) / kWave, kMaxLaunchWaveBlocks, [&](int64_t b0, unsigned nb) {
         if (vec)
             hipLaunchKernelGGL(k_sddmm<true>, dim3(nb), dim3(kWave), 0, static_cast<hipStream_t>(stream),
                                indptr, indices, n_rows, b0 * kWave, nnz, G, ldg, X, ldx, d, perm, out);

@@ -1051,7 +1051,7 @@ int launch_spmm(const IP* indptr, const int32_t* indices, const float* vals, int
     const int nr = (int)m_rows, nh = (int)n_heavy;
     const int pu = (flags & SRG_SPMM_PACKED_U2) ? 2 : kPackedU;
     const unsigned shm = (unsigned)spmm_lds_bytes(flags);
-    const int rc = launch_chunks(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    const int rc = launch_chunks_capped(blocks, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         const dim3 grid(nb);
         const int bb = (int)b0;
 #define SRG_LAUNCH_SPMM(V, F, SF)                                                               \

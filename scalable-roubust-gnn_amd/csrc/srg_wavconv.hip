@@ -182,7 +182,7 @@ int launch_scaled(int64_t n_rows, hipStream_t s, const int64_t* ip, const int32_
                   const float* scale, int axis, const float* X, int64_t ldx, float* Y, int64_t ldy, int d)
 {
     constexpr int kRows = 4 * (kWave / W);                  // rows per 256-lane workgroup
-    return launch_chunks((n_rows + kRows - 1) / kRows, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
+    return launch_chunks_capped((n_rows + kRows - 1) / kRows, kMaxLaunchBlocks, [&](int64_t b0, unsigned nb) {
         const int64_t r0 = b0 * kRows;
         hipLaunchKernelGGL(k_spmm_scaled<W>, dim3(nb), dim3(256), 0, s, ip + r0, ix, vv,
                            (scale && axis == 1) ? scale + r0 : scale, axis, n_rows - r0, X, ldx, Y + r0 * ldy, ldy,
@@ -237,7 +237,7 @@ int srg_sddmm_rowsum_f32(const int64_t* indptr, const int32_t* indices, const fl
         SRG_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n_rows * sizeof(float), s));
         return srg_ok();
     }
-    const int rc = launch_chunks(n_rows, kMaxLaunchWaveBlocks, [&](int64_t r0, unsigned nb) {   // a row per block
+    const int rc = launch_chunks_capped(n_rows, kMaxLaunchWaveBlocks, [&](int64_t r0, unsigned nb) {   // a row per block
         hipLaunchKernelGGL(k_sddmm_rowsum, dim3(nb), dim3(kWave), 0, s, indptr + r0, indices, values, G, ldg,
                            P + r0 * ldp, ldp, d, out + r0);
         return launch_status();

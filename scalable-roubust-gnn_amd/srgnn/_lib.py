@@ -182,6 +182,8 @@ EXPORTED_SYMBOLS = (
     "srg_last_error_code",
     "srg_clear_error",
     "srg_version",
+    "srg_debug_launch_cap",
+    "srg_debug_chunk_launches",
 )
 
 
@@ -370,6 +372,10 @@ def _declare(lib):
     lib.srg_clear_error.restype = None
     lib.srg_version.argtypes = []
     lib.srg_version.restype = ctypes.c_char_p
+    lib.srg_debug_launch_cap.argtypes = [_i64]
+    lib.srg_debug_launch_cap.restype = _i64
+    lib.srg_debug_chunk_launches.argtypes = []
+    lib.srg_debug_chunk_launches.restype = _i64
     lib.FloatCSRMulDense.restype = ctypes.c_int
     return lib
 
@@ -438,6 +444,36 @@ class hub_forked:
 
     def __exit__(self, *exc):
         self.join()
+        return False
+
+
+class launch_cap:
+    """Test hook (srg_debug_launch_cap): inside the block no launch of the library has more than `n` blocks,
+    so chunked launches go out in several chunks and grid-stride kernels take several trips -- the same
+    results, scheduled differently.  Leaving the block, normally or by an exception, restores the bound
+    that held before; `launches` is then the number of chunk launches made inside it
+    (srg_debug_chunk_launches; `launches` reads the running count while the block is open)."""
+
+    def __init__(self, n: int):
+        self.n = int(n)
+        self._start = self._end = None
+        self._prev = 0
+
+    def __enter__(self):
+        self._start = lib().srg_debug_chunk_launches()
+        self._prev = lib().srg_debug_launch_cap(self.n)
+        return self
+
+    @property
+    def launches(self) -> int:
+        end = self._end if self._end is not None else lib().srg_debug_chunk_launches()
+        return end - self._start
+
+    def __exit__(self, *exc):
+        try:
+            self._end = lib().srg_debug_chunk_launches()
+        finally:
+            lib().srg_debug_launch_cap(self._prev)
         return False
 
 
