@@ -1,5 +1,6 @@
 // srg_device.h -- device code that more than one kernel family uses: vector loads and stores, the chain
-// link and the epilogue arithmetic, the row-wave gather, the filtered row walk, the launch constants; and
+// link and the epilogue arithmetic, the row-wave gather, the filtered row walk, the rows-by-lanes layout of
+// the streaming reductions, the launch constants; and
 // the host checks that go with them, the vector-width check among them.  Everything is in the anonymous
 // namespace: each translation unit that includes this header compiles its own copy into its own kernels.
 // Not part of the C-ABI (include/srgnn_hip.h).
@@ -247,9 +248,58 @@ __device__ __forceinline__ int wave_slot(int block_base)
 }
 
 // ------------------------------------------------------------------------------------------------
+// rows by lanes: the layout of the streaming passes that reduce along a row (the hop attention's dot
+// products, the NAFS step)
+//
+// S = 2^lgS lanes per row (the power of two >= the row's VEC-chunks, at most 64), R = 64 / S rows per wave
+// step.  Lane c0 of row group g takes chunks c0, c0 + S, ... of row base + g, base = first, first + stride,
+// ... (grid-stride over the wave steps); the S partials of a row are added in an xor butterfly, in which
+// both partners add the same two values, so every lane of the row holds the same sum.  Every lane of the
+// wave runs every step, for the butterfly reads its partners.  A row's bits depend on d and VEC only, never
+// on the grid, the row count or the wave that got the row.
+// ------------------------------------------------------------------------------------------------
+struct RowLanes {
+    int S, R, g, c0;
+    int64_t first, stride;
+    // block_dim: the kernel's blockDim.x, read there (read in here, behind a call boundary, it compiles to the
+    // lookup that allows for a partial last workgroup, which HIP never launches)
+    __device__ __forceinline__ RowLanes(int lgS, unsigned block_dim)
+    {
+        S = 1 << lgS, R = 64 >> lgS;
+        const int lane = threadIdx.x & 63;
+        g = lane >> lgS, c0 = lane & (S - 1);
+        const int64_t wave = (int64_t)blockIdx.x * (block_dim >> 6) + (threadIdx.x >> 6);
+        const int64_t waves = (int64_t)gridDim.x * (block_dim >> 6);
+        first = wave * R, stride = waves * R;
+    }
+};
+
+// the butterfly over S lanes, every add correctly rounded; several sums go through it side by side
+template <typename... F>
+__device__ __forceinline__ void butterfly_add(int S, F&... x)
+{
+    for (int m = S >> 1; m > 0; m >>= 1) ((x = __fadd_rn(x, __shfl_xor(x, m))), ...);
+}
+
+// ------------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------------
 constexpr int kUnroll = 8;
+
+// lgS of rows of cpr chunks and the RowLanes kernels' grid over n_rows rows: 256-thread workgroups, one
+// wave step each wave, clipped to 256 * 64 workgroups (the kernels stride over the rest)
+struct RowLanesGrid {
+    int lgS;
+    unsigned blocks;
+};
+RowLanesGrid row_lanes_grid(int cpr, int64_t n_rows)
+{
+    int lgS = 0;
+    while (lgS < 6 && (1 << lgS) < cpr) ++lgS;
+    const int64_t rows_per_block = (int64_t)(256 / 64) * (64 >> lgS);
+    const int64_t blocks = (n_rows + rows_per_block - 1) / rows_per_block;
+    return {lgS, (unsigned)(blocks < 256 * 64 ? blocks : 256 * 64)};
+}
 
 bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 

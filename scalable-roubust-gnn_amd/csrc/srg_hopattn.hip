@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "srgnn_hip.h"
 #include "srg_internal.h"
@@ -61,18 +62,38 @@ __device__ __forceinline__ typename Vec<float, VEC>::type panel_load(const float
     return vload<float, VEC>(p);
 }
 
+// One lane's share of the dot products of a panel row with N vectors: chunks rl.c0, rl.c0 + S, ... of the
+// row at xr, one load of a chunk feeding N fma chains in chunk and element order, acc[k] = fma(v[k][e],
+// x[e], acc[k]).  A chain starts from what the caller put into acc[k]; a vector with use[k] false is
+// neither loaded nor folded (use is wave-uniform; constants fold away).
+template <int VEC, bool ROWS, int N>
+__device__ __forceinline__ void chunk_dots(const RowLanes& rl, const float* xr, bool live, bool readable, int cpr,
+                                           const float* const (&v)[N], const bool (&use)[N], float (&acc)[N])
+{
+    typedef typename Vec<float, VEC>::type V;
+    for (int c = rl.c0; live && c < cpr; c += rl.S) {
+        const V xc = panel_load<VEC, ROWS>(xr + (int64_t)c * VEC, readable);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            if (!use[k]) continue;
+            const V vc = vload<float, VEC>(v[k] + (int64_t)c * VEC);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) acc[k] = __builtin_fmaf(elem(vc, j), elem(xc, j), acc[k]);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // scores: zflat[h * n + i] = (ref(i) + hop(h, i)) + b   (gate: hop(h, i) + b)
 //   ref(i)    = sum over the reference panels t ascending, columns in lane order, of w[t*d + c] * F_t[i, c]
 //   hop(h, i) = sum over the columns of w[R + c] * F_{start+h}[i, c],  R = the reference part's length
-// The lane layout is k_hop_simweight's: S = 2^lgS lanes per row (the power of two >= the row's
-// VEC-chunks, at most 64), 64 / S rows per wave step, lane c0 of a row takes chunks c0, c0 + S, ... and
-// folds them with fmas in that order -- the reference part as ONE chain per lane that runs on through the
-// panels t = 0, 1, ..., each hop part as a chain of its own from +0 -- and the S partials are added in an
-// xor butterfly.  A panel row is loaded once and feeds both parts.  A hop part waits in zflat (written
-// and read back by the same lane) until the last reference panel is folded in.  A row's bits depend on
-// d, T, the slice and VEC only.  (Loading the rows of four panels ahead of the first fold measured slower,
-// 0.49 against 0.30 ms at n = 200,000, T = 11, d = 128: 100 registers per lane instead of 30.)
+// Rows by lanes (RowLanes, srg_device.h), the chunks folded by chunk_dots -- the reference part as ONE
+// chain per lane that runs on through the panels t = 0, 1, ..., each hop part as a chain of its own from
+// +0 -- and the S partials added by butterfly_add.  A panel row is loaded once and feeds both parts.  A hop
+// part waits in zflat (written and read back by the same lane) until the last reference panel is folded
+// in.  A row's bits depend on d, T, the slice and VEC only.  (Loading the rows of four panels ahead of the
+// first fold measured slower, 0.49 against 0.30 ms at n = 200,000, T = 11, d = 128: 100 registers per lane
+// instead of 30.)
 // ------------------------------------------------------------------------------------------------
 template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
@@ -80,17 +101,13 @@ k_hop_scores(HopPanels pl, int T, int start, int H, int kind, const float* __res
              const float* __restrict__ b, float* __restrict__ zflat, int64_t n, int d, int cpr, int lgS,
              const int64_t* __restrict__ rows, int64_t n_src)
 {
-    typedef typename Vec<float, VEC>::type V;
-    const int S = 1 << lgS, R = 64 >> lgS;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> lgS, c0 = lane & (S - 1);
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const RowLanes rl(lgS, blockDim.x);
+    const int S = rl.S, c0 = rl.c0;
     const float* wh = w + ref_dim(kind, T, d);
     const float bias = b[0];
     // every lane of the wave runs every step (the butterfly reads its partners); rows past the end load nothing
-    for (int64_t base = wave * R; base < n; base += waves * R) {
-        const int64_t r = base + g;
+    for (int64_t base = rl.first; base < n; base += rl.stride) {
+        const int64_t r = base + rl.g;
         const bool live = r < n;
         bool readable;
         const int64_t pr = panel_row<ROWS>(rows, n_src, r, live, readable);
@@ -99,28 +116,17 @@ k_hop_scores(HopPanels pl, int T, int start, int H, int kind, const float* __res
             const int h = t - start;
             const bool hop = h >= 0 && h < H, rf = is_ref(kind, t);
             if (!hop && !rf) continue;
-            const float* xr = pl.p[t] + pr * pl.ld[t];
-            const float* wr = w + (int64_t)t * d;
-            float hp = 0.0f;
-            for (int c = c0; live && c < cpr; c += S) {
-                const V xc = panel_load<VEC, ROWS>(xr + (int64_t)c * VEC, readable);
-                if (rf) {
-                    const V wc = vload<float, VEC>(wr + (int64_t)c * VEC);
-#pragma unroll
-                    for (int j = 0; j < VEC; ++j) ref = __builtin_fmaf(elem(wc, j), elem(xc, j), ref);
-                }
-                if (hop) {
-                    const V wc = vload<float, VEC>(wh + (int64_t)c * VEC);
-#pragma unroll
-                    for (int j = 0; j < VEC; ++j) hp = __builtin_fmaf(elem(wc, j), elem(xc, j), hp);
-                }
-            }
+            const float* const v[2] = {w + (int64_t)t * d, wh};
+            const bool use[2] = {rf, hop};
+            float acc[2] = {ref, 0.0f};
+            chunk_dots<VEC, ROWS>(rl, pl.p[t] + pr * pl.ld[t], live, readable, cpr, v, use, acc);
+            ref = acc[0];
             if (hop) {
-                for (int m = S >> 1; m > 0; m >>= 1) hp = __fadd_rn(hp, __shfl_xor(hp, m));
-                if (live && c0 == (h & (S - 1))) zflat[(int64_t)h * n + r] = hp;
+                butterfly_add(S, acc[1]);
+                if (live && c0 == (h & (S - 1))) zflat[(int64_t)h * n + r] = acc[1];
             }
         }
-        for (int m = S >> 1; m > 0; m >>= 1) ref = __fadd_rn(ref, __shfl_xor(ref, m));
+        butterfly_add(S, ref);
         for (int h = c0; live && h < H; h += S) {
             float z = zflat[(int64_t)h * n + r];
             if (kind != SRG_HOP_GATE) z = __fadd_rn(ref, z);
@@ -164,18 +170,14 @@ k_hop_combine(HopPanels pl, int start, int H, const float* __restrict__ P, float
               int64_t n, int cpr, int lgS, const int64_t* __restrict__ rows, int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
-    const int S = 1 << lgS, R = 64 >> lgS;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> lgS, c0 = lane & (S - 1);
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t base = wave * R; base < n; base += waves * R) {
-        const int64_t r = base + g;
+    const RowLanes rl(lgS, blockDim.x);
+    for (int64_t base = rl.first; base < n; base += rl.stride) {
+        const int64_t r = base + rl.g;
         if (r >= n) continue;
         bool readable;
         const int64_t xr = panel_row<ROWS>(rows, n_src, r, true, readable);
         const float* pr = P + r * H;
-        for (int c = c0; c < cpr; c += S) {
+        for (int c = rl.c0; c < cpr; c += rl.S) {
             V acc;
 #pragma unroll 4
             for (int h = 0; h < H; ++h) {
@@ -192,36 +194,25 @@ k_hop_combine(HopPanels pl, int start, int H, const float* __restrict__ P, float
     }
 }
 
-// dP[i, h] = G[i, :] . F_{start+h}[i, :]: the scores' lane layout, one fma chain per lane from +0 in chunk
-// order, xor butterfly.  HOP_MAJOR stores dP[h * n + i] (the recursive attention's per-row vectors).
+// dP[i, h] = G[i, :] . F_{start+h}[i, :]: rows by lanes, chunk_dots' one fma chain per lane from +0,
+// butterfly_add.  HOP_MAJOR stores dP[h * n + i] (the recursive attention's per-row vectors).
 template <int VEC, bool HOP_MAJOR, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_rowdots(HopPanels pl, int start, int H, const float* __restrict__ G, int64_t ldg, float* __restrict__ dP,
               int64_t n, int cpr, int lgS, const int64_t* __restrict__ rows, int64_t n_src)
 {
-    typedef typename Vec<float, VEC>::type V;
-    const int S = 1 << lgS, R = 64 >> lgS;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> lgS, c0 = lane & (S - 1);
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t base = wave * R; base < n; base += waves * R) {
-        const int64_t r = base + g;
+    const RowLanes rl(lgS, blockDim.x);
+    for (int64_t base = rl.first; base < n; base += rl.stride) {
+        const int64_t r = base + rl.g;
         const bool live = r < n;
         bool readable;
         const int64_t pr = panel_row<ROWS>(rows, n_src, r, live, readable);
-        const float* gr = G + r * ldg;
+        const float* const v[1] = {G + r * ldg};
         for (int h = 0; h < H; ++h) {
-            const float* xr = pl.p[start + h] + pr * pl.ld[start + h];
-            float dot = 0.0f;
-            for (int c = c0; live && c < cpr; c += S) {
-                const V xc = panel_load<VEC, ROWS>(xr + (int64_t)c * VEC, readable);
-                const V gc = vload<float, VEC>(gr + (int64_t)c * VEC);
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) dot = __builtin_fmaf(elem(gc, j), elem(xc, j), dot);
-            }
-            for (int m = S >> 1; m > 0; m >>= 1) dot = __fadd_rn(dot, __shfl_xor(dot, m));
-            if (live && c0 == (h & (S - 1))) dP[HOP_MAJOR ? (int64_t)h * n + r : r * H + h] = dot;
+            float dot[1] = {0.0f};
+            chunk_dots<VEC, ROWS>(rl, pl.p[start + h] + pr * pl.ld[start + h], live, readable, cpr, v, {true}, dot);
+            butterfly_add(rl.S, dot[0]);
+            if (live && rl.c0 == (h & (rl.S - 1))) dP[HOP_MAJOR ? (int64_t)h * n + r : r * H + h] = dot[0];
         }
     }
 }
@@ -265,14 +256,37 @@ k_hop_dzsum(const float* __restrict__ dzflat, float* __restrict__ s, int64_t n, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// parameter gradient, stage 1.  Group q owns rows [q * rpg, (q + 1) * rpg); CT = 2^lgCT threads of a
-// workgroup serve one group (256 / CT groups per workgroup), thread c0 owning the VEC columns of chunk
-// tile * CT + c0 (blockIdx.y = tile: wide rows take more tiles, not more registers).  Per panel t, rows
-// ascending, one fma per row and column:
-//   ref_t[c] = fma(s[i], F_t[i, c], ref_t[c])              -> partials[q, t*d + c]
-//   hop_h[c] = fma(dz[h, i], F_t[i, c], hop_h[c]), h = t - start
-// a panel row loaded once for both; the hop parts are added in ascending h (the first as it is) into
-// partials[q, R + c]; the group's bias part s[i0] + s[i0+1] + ... goes to partials[q, in_dim].
+// parameter gradient, both attentions: in_dim weights and the bias, summed over the rows in two stages.
+// The scratch of the two stages, laid out in one place: s_floats floats of s (the per-row factor of the
+// bias), then n_groups rows of ldq floats, row q the partial sums of group q = rows [q * rpg, (q + 1) *
+// rpg): in_dim weight columns and the bias column, each row of either rounded up to 16 bytes.  The
+// scratch queries, the hosts and both stages take it from here; the kernels get it by value.
+// ------------------------------------------------------------------------------------------------
+int64_t rows_per_group(int64_t n)   // a function of n alone (srgnn_hip.h)
+{
+    int64_t rpg = 32;
+    while (rpg * 2048 < n) rpg *= 2;
+    return rpg;
+}
+struct WgradLayout {
+    int64_t rpg, n_groups, ldq, s_floats, in_dim;
+    WgradLayout(int64_t n, int64_t in_dim)
+        : rpg(rows_per_group(n)), n_groups((n + rpg - 1) / rpg), ldq(pad4(in_dim + 1)), s_floats(pad4(n)),
+          in_dim(in_dim) {}
+    int64_t bytes() const { return (s_floats + n_groups * ldq) * (int64_t)sizeof(float); }
+};
+
+// ------------------------------------------------------------------------------------------------
+// stage 1.  CT = 2^lgCT threads of a workgroup serve one group (256 / CT groups per workgroup), thread c0
+// owning the VEC columns of chunk c = tile * CT + c0 (blockIdx.y = tile: wide rows take more tiles, not more
+// registers).  Per panel, rows ascending, two fma chains per column from one load of the panel
+// row, chain a on the rows' factor a[i] and chain b on b[i]:
+//   learnable   a = s, for a reference panel t                 -> partials[q, t*d + c]
+//               b = dz[h, :], h = t - start in the slice        totalled over h -> partials[q, R + c]
+//   recursive   a = dzp[h, :]                                   totalled over h -> partials[q, c]
+//               b = dzq[h, :]                                   totalled over h -> partials[q, d + c]
+// a total adds the panels' chains in ascending h, the first as it is.  The group's bias part s[i0] +
+// s[i0+1] + ... goes to partials[q, in_dim].
 // ------------------------------------------------------------------------------------------------
 
 // The row loop of stage 1 under an index: fold(i, F[rows[i], chunk]) for i = i0 .. i1-1 ascending, ROWS_STEP
@@ -326,26 +340,26 @@ __device__ __forceinline__ void indexed_rows(const float* x, int64_t ldx, const 
     }
 }
 
+// The learnable attention's stage 1.  The two stage-1 kernels share the layout and the host and keep their
+// prologue, row loops and totals as written, on purpose: each shared form of them measured slower.
 template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_wgrad_partial(HopPanels pl, int T, int start, int H, int kind, const float* __restrict__ dzflat,
-                    const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d, int cpr, int lgCT,
-                    int64_t rpg, int64_t n_groups, int want_w, const int64_t* __restrict__ rows, int64_t n_src)
+                    const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d,
+                    int cpr, int lgCT, WgradLayout L, int want_w, const int64_t* __restrict__ rows, int64_t n_src)
 {
     typedef typename Vec<float, VEC>::type V;
     const int CT = 1 << lgCT;
     const int c0 = threadIdx.x & (CT - 1);
     const int64_t q = (int64_t)blockIdx.x * (256 >> lgCT) + (threadIdx.x >> lgCT);
-    if (q >= n_groups) return;
+    if (q >= L.n_groups) return;
     const int c = blockIdx.y * CT + c0;
-    const int rd = ref_dim(kind, T, d);
-    const int64_t ldq = pad4((int64_t)rd + d + 1);
-    float* out = partials + q * ldq;
-    const int64_t i0 = q * rpg, i1 = i0 + rpg < n ? i0 + rpg : n;
+    float* out = partials + q * L.ldq;
+    const int64_t i0 = q * L.rpg, i1 = i0 + L.rpg < n ? i0 + L.rpg : n;
     if (c == 0) {
         float t = s[i0];
         for (int64_t i = i0 + 1; i < i1; ++i) t = __fadd_rn(t, s[i]);
-        out[rd + d] = t;
+        out[L.in_dim] = t;
     }
     if (!want_w || c >= cpr) return;
     V tot;
@@ -383,22 +397,78 @@ k_hop_wgrad_partial(HopPanels pl, int T, int start, int H, int kind, const float
             for (int j = 0; j < VEC; ++j) elem(tot, j) = h == 0 ? elem(ha, j) : __fadd_rn(elem(tot, j), elem(ha, j));
         }
     }
-    vstore<float, VEC>(out + rd + (int64_t)c * VEC, tot, false);
+    vstore<float, VEC>(out + (L.in_dim - d) + (int64_t)c * VEC, tot, false);
+}
+
+// The recursive attention's stage 1: every panel feeds both chains.
+template <int VEC, bool ROWS>
+__global__ void __launch_bounds__(256)
+k_hop_recur_wgrad_partial(HopPanels pl, int H, const float* __restrict__ dzp, const float* __restrict__ dzq,
+                          const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d,
+                          int cpr, int lgCT, WgradLayout L, int want_w, const int64_t* __restrict__ rows, int64_t n_src)
+{
+    typedef typename Vec<float, VEC>::type V;
+    const int CT = 1 << lgCT;
+    const int c0 = threadIdx.x & (CT - 1);
+    const int64_t q = (int64_t)blockIdx.x * (256 >> lgCT) + (threadIdx.x >> lgCT);
+    if (q >= L.n_groups) return;
+    const int c = blockIdx.y * CT + c0;
+    float* out = partials + q * L.ldq;
+    const int64_t i0 = q * L.rpg, i1 = i0 + L.rpg < n ? i0 + L.rpg : n;
+    if (c == 0) {
+        float t = s[i0];
+        for (int64_t i = i0 + 1; i < i1; ++i) t = __fadd_rn(t, s[i]);
+        out[L.in_dim] = t;
+    }
+    if (!want_w || c >= cpr) return;
+    V toth, totc;
+    for (int h = 0; h < H; ++h) {
+        const float* x = pl.p[h] + (int64_t)c * VEC;
+        const int64_t ldx = pl.ld[h];
+        const float* dp = dzp + (int64_t)h * n;
+        const float* dq = dzq + (int64_t)h * n;
+        V ha = vzero<float, VEC>(), ca = vzero<float, VEC>();
+        if constexpr (ROWS) {
+            indexed_rows<VEC>(x, ldx, rows, n_src, i0, i1, dp, dq, [&](float pi, float qi, const V& xc) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
+                    elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
+                }
+            });
+        } else {
+#pragma unroll 4
+            for (int64_t i = i0; i < i1; ++i) {
+                const V xc = vload<float, VEC>(x + i * ldx);
+                const float pi = dp[i], qi = dq[i];
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
+                    elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            elem(toth, j) = h == 0 ? elem(ha, j) : __fadd_rn(elem(toth, j), elem(ha, j));
+            elem(totc, j) = h == 0 ? elem(ca, j) : __fadd_rn(elem(totc, j), elem(ca, j));
+        }
+    }
+    vstore<float, VEC>(out + (int64_t)c * VEC, toth, false);
+    vstore<float, VEC>(out + d + (int64_t)c * VEC, totc, false);
 }
 
 // stage 2: column j of the partials folded in group order, the first as it is
 __global__ void __launch_bounds__(256)
-k_hop_wgrad_fold(const float* __restrict__ partials, int64_t n_groups, int in_dim, float* __restrict__ dw,
-                 float* __restrict__ db)
+k_hop_wgrad_fold(const float* __restrict__ partials, WgradLayout L, float* __restrict__ dw, float* __restrict__ db)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j > in_dim) return;
-    const int64_t ldq = pad4((int64_t)in_dim + 1);
-    if (j < in_dim ? dw == nullptr : db == nullptr) return;
+    if (j > L.in_dim) return;
+    if (j < L.in_dim ? dw == nullptr : db == nullptr) return;
     float t = partials[j];
 #pragma unroll 32
-    for (int64_t q = 1; q < n_groups; ++q) t = __fadd_rn(t, partials[q * ldq + j]);
-    if (j < in_dim) dw[j] = t; else db[0] = t;
+    for (int64_t q = 1; q < L.n_groups; ++q) t = __fadd_rn(t, partials[q * L.ldq + j]);
+    if (j < L.in_dim) dw[j] = t; else db[0] = t;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -406,46 +476,28 @@ k_hop_wgrad_fold(const float* __restrict__ partials, int64_t n_groups, int in_di
 // row of Linear(2d, 1); w_c . (sum_j W_j F_j[i, :]) = sum_j W_j (w_c . F_j[i, :]), so between the panels and
 // the final weighted sum the operator is a scalar recurrence per row on the 2H dot products below.
 //
-// zp[h * n + i] = w_h . F_h[i, :], zq[h * n + i] = w_c . F_h[i, :]: k_hop_rowdots' lane layout, two fma
-// chains per lane from +0 in chunk order from one load of the panel row, one butterfly each.
+// zp[h * n + i] = w_h . F_h[i, :], zq[h * n + i] = w_c . F_h[i, :]: rows by lanes, chunk_dots' two fma chains
+// per lane from +0 from one load of the panel row, both through one butterfly_add.
 // ------------------------------------------------------------------------------------------------
 template <int VEC, bool ROWS>
 __global__ void __launch_bounds__(256)
 k_hop_recur_scores(HopPanels pl, int H, const float* __restrict__ w, float* __restrict__ zp, float* __restrict__ zq,
                    int64_t n, int d, int cpr, int lgS, const int64_t* __restrict__ rows, int64_t n_src)
 {
-    typedef typename Vec<float, VEC>::type V;
-    const int S = 1 << lgS, R = 64 >> lgS;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> lgS, c0 = lane & (S - 1);
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    const float* wc = w + d;
-    for (int64_t base = wave * R; base < n; base += waves * R) {
-        const int64_t r = base + g;
+    const RowLanes rl(lgS, blockDim.x);
+    const float* const v[2] = {w, w + d};
+    for (int64_t base = rl.first; base < n; base += rl.stride) {
+        const int64_t r = base + rl.g;
         const bool live = r < n;
         bool readable;
         const int64_t pr = panel_row<ROWS>(rows, n_src, r, live, readable);
         for (int h = 0; h < H; ++h) {
-            const float* xr = pl.p[h] + pr * pl.ld[h];
-            float p = 0.0f, q = 0.0f;
-            for (int c = c0; live && c < cpr; c += S) {
-                const V xc = panel_load<VEC, ROWS>(xr + (int64_t)c * VEC, readable);
-                const V hc = vload<float, VEC>(w + (int64_t)c * VEC);
-                const V cc = vload<float, VEC>(wc + (int64_t)c * VEC);
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) {
-                    p = __builtin_fmaf(elem(hc, j), elem(xc, j), p);
-                    q = __builtin_fmaf(elem(cc, j), elem(xc, j), q);
-                }
-            }
-            for (int m = S >> 1; m > 0; m >>= 1) {
-                p = __fadd_rn(p, __shfl_xor(p, m));
-                q = __fadd_rn(q, __shfl_xor(q, m));
-            }
-            if (live && c0 == (h & (S - 1))) {
-                zp[(int64_t)h * n + r] = p;
-                zq[(int64_t)h * n + r] = q;
+            float z[2] = {0.0f, 0.0f};
+            chunk_dots<VEC, ROWS>(rl, pl.p[h] + pr * pl.ld[h], live, readable, cpr, v, {true, true}, z);
+            butterfly_add(rl.S, z[0], z[1]);
+            if (live && rl.c0 == (h & (rl.S - 1))) {
+                zp[(int64_t)h * n + r] = z[0];
+                zq[(int64_t)h * n + r] = z[1];
             }
         }
     }
@@ -589,99 +641,33 @@ k_hop_recur_backward(const float* __restrict__ zq, const float* __restrict__ wor
     }
 }
 
-// Parameter gradient of the recursive attention, stage 1: k_hop_wgrad_partial's groups, tiles and rows-
-// ascending fma chains, two chains per panel and column from one load,
-//   hp_h[c] = fma(dzp[h, i], F_h[i, c], hp_h[c])      cp_h[c] = fma(dzq[h, i], F_h[i, c], cp_h[c])
-// each kind added over h ascending (the first as it is) into partials[q, c] and partials[q, d + c]; the
-// group's bias part s[i0] + s[i0+1] + ... (s[i] = dzp[0, i] + dzp[1, i] + ...) goes to partials[q, 2d].
-template <int VEC, bool ROWS>
-__global__ void __launch_bounds__(256)
-k_hop_recur_wgrad_partial(HopPanels pl, int H, const float* __restrict__ dzp, const float* __restrict__ dzq,
-                          const float* __restrict__ s, float* __restrict__ partials, int64_t n, int d, int cpr,
-                          int lgCT, int64_t rpg, int64_t n_groups, int want_w, const int64_t* __restrict__ rows,
-                          int64_t n_src)
-{
-    typedef typename Vec<float, VEC>::type V;
-    const int CT = 1 << lgCT;
-    const int c0 = threadIdx.x & (CT - 1);
-    const int64_t q = (int64_t)blockIdx.x * (256 >> lgCT) + (threadIdx.x >> lgCT);
-    if (q >= n_groups) return;
-    const int c = blockIdx.y * CT + c0;
-    const int64_t ldq = pad4((int64_t)2 * d + 1);
-    float* out = partials + q * ldq;
-    const int64_t i0 = q * rpg, i1 = i0 + rpg < n ? i0 + rpg : n;
-    if (c == 0) {
-        float t = s[i0];
-        for (int64_t i = i0 + 1; i < i1; ++i) t = __fadd_rn(t, s[i]);
-        out[2 * d] = t;
-    }
-    if (!want_w || c >= cpr) return;
-    V toth, totc;
-    for (int h = 0; h < H; ++h) {
-        const float* x = pl.p[h] + (int64_t)c * VEC;
-        const int64_t ldx = pl.ld[h];
-        const float* dp = dzp + (int64_t)h * n;
-        const float* dq = dzq + (int64_t)h * n;
-        V ha = vzero<float, VEC>(), ca = vzero<float, VEC>();
-        if constexpr (ROWS) {
-            indexed_rows<VEC>(x, ldx, rows, n_src, i0, i1, dp, dq, [&](float pi, float qi, const V& xc) {
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) {
-                    elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
-                    elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
-                }
-            });
-        } else {
-#pragma unroll 4
-            for (int64_t i = i0; i < i1; ++i) {
-                const V xc = vload<float, VEC>(x + i * ldx);
-                const float pi = dp[i], qi = dq[i];
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) {
-                    elem(ha, j) = __builtin_fmaf(pi, elem(xc, j), elem(ha, j));
-                    elem(ca, j) = __builtin_fmaf(qi, elem(xc, j), elem(ca, j));
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            elem(toth, j) = h == 0 ? elem(ha, j) : __fadd_rn(elem(toth, j), elem(ha, j));
-            elem(totc, j) = h == 0 ? elem(ca, j) : __fadd_rn(elem(totc, j), elem(ca, j));
-        }
-    }
-    vstore<float, VEC>(out + (int64_t)c * VEC, toth, false);
-    vstore<float, VEC>(out + d + (int64_t)c * VEC, totc, false);
-}
-
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 struct HopShape {
     HopPanels pl;
     int vec, cpr, lgS;
-    unsigned row_blocks;      // the row-streaming kernels' grid (grid-stride over the row steps)
+    bool empty;               // n == 0: nothing to launch, and nothing else here is set
+    unsigned row_blocks;      // the row-streaming kernels' grid (row_lanes_grid)
     unsigned thread_blocks;   // the one-thread-per-row kernels' grid
 };
 
-// rows per group of the parameter gradient's stage 1: a function of n alone (srgnn_hip.h)
-int64_t rows_per_group(int64_t n)
+// The head of every *_rows_* entry after its own flag checks: the row index (NULL is the identity, n_src is
+// not looked at), the hop list and the slice; then the access width every row of every panel and of `wide` is
+// aligned for, and the grids.  wide: the one operand besides the panels that the entry reads or writes in
+// chunks (NULL: none), ld_name its row stride's name in the error text (NULL for a vector, ld = 0).
+int hop_shape(const int64_t* rows, int64_t n_src, const float* const* panels, const int64_t* ldp, int T, int start,
+              int end, int64_t n, int d, const Operand* wide, const char* ld_name, HopShape& hs)
 {
-    int64_t rpg = 32;
-    while (rpg * 2048 < n) rpg *= 2;
-    return rpg;
-}
-
-// Checks the hop list and the slice, and picks the access width every row of every panel and of the
-// `wide` operands (read or written in chunks: pointer and row stride, 0 for a vector) is aligned for.
-int hop_shape(const float* const* panels, const int64_t* ldp, int T, int start, int end, int64_t n, int d,
-              const void* const* wide, const int64_t* wide_ld, int n_wide, HopShape& hs)
-{
+    if (rows && n_src < 0) return srg_fail(SRG_ERR_INVALID, "n_src=%lld panel rows", (long long)n_src);
+    if (ld_name && wide->ld < d) return srg_fail(SRG_ERR_INVALID, "%s=%lld < d=%d", ld_name, (long long)wide->ld, d);
     if (T < 1 || T > SRG_HOP_MAX) return srg_fail(SRG_ERR_INVALID, "T=%d hop panels: 1 .. %d", T, SRG_HOP_MAX);
     if (start < 0 || end <= start || end > T)
         return srg_fail(SRG_ERR_INVALID, "hop slice [%d, %d) of %d panels", start, end, T);
     if (n < 0 || d < 1) return srg_fail(SRG_ERR_INVALID, "bad shape n=%lld d=%d", (long long)n, d);
     if ((int64_t)T * d + d + 1 > INT32_MAX) return srg_fail(SRG_ERR_INVALID, "T*d = %d*%d too wide", T, d);
-    if (n == 0) return SRG_OK;
+    hs.empty = n == 0;
+    if (hs.empty) return SRG_OK;
     if (!panels || !ldp) return srg_fail(SRG_ERR_INVALID, "null panel list");
     for (int t = 0; t < T; ++t) {
         if (!panels[t] || ldp[t] < d)
@@ -691,20 +677,17 @@ int hop_shape(const float* const* panels, const int64_t* ldp, int T, int start, 
         hs.pl.ld[t] = ldp[t];
     }
     for (int t = T; t < SRG_HOP_MAX; ++t) { hs.pl.p[t] = nullptr; hs.pl.ld[t] = 0; }
-    for (int e = 0; e < n_wide; ++e)
-        if (!wide[e]) return srg_fail(SRG_ERR_INVALID, "null pointer");
+    if (wide && !wide->p) return srg_fail(SRG_ERR_INVALID, "null pointer");
     hs.vec = 1;
     for (int v = 4; v > 1 && hs.vec == 1; v >>= 1) {
-        bool ok = true;
+        bool ok = !wide || rows_aligned(v, sizeof(float), d, {{wide->p, wide->ld}});
         for (int t = 0; ok && t < T; ++t) ok = rows_aligned(v, sizeof(float), d, {{panels[t], ldp[t]}});
-        for (int e = 0; ok && e < n_wide; ++e) ok = rows_aligned(v, sizeof(float), d, {{wide[e], wide_ld[e]}});
         if (ok) hs.vec = v;
     }
     hs.cpr = d / hs.vec;
-    hs.lgS = 0;
-    while (hs.lgS < 6 && (1 << hs.lgS) < hs.cpr) ++hs.lgS;
-    const int64_t rows_per_block = (int64_t)(256 / 64) * (64 >> hs.lgS);
-    hs.row_blocks = (unsigned)std::min<int64_t>((n + rows_per_block - 1) / rows_per_block, 256 * 64);
+    const RowLanesGrid rg = row_lanes_grid(hs.cpr, n);
+    hs.lgS = rg.lgS;
+    hs.row_blocks = rg.blocks;
     hs.thread_blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 256 * 16);
     return SRG_OK;
 }
@@ -726,21 +709,48 @@ int check_pairing(int pairing)
     return SRG_OK;
 }
 
-// LAUNCH(VEC, ROWS) under the panels' access width; ROWS = true with an index, the identity kernels without
-#define SRG_HOP_BY_VEC(vec, rows, LAUNCH)   \
-    do {                                    \
-        if (rows) {                         \
-            if ((vec) == 4) { LAUNCH(4, true); } else if ((vec) == 2) { LAUNCH(2, true); } else { LAUNCH(1, true); } \
-        } else {                            \
-            if ((vec) == 4) { LAUNCH(4, false); } else if ((vec) == 2) { LAUNCH(2, false); } else { LAUNCH(1, false); } \
-        }                                   \
-    } while (0)
-
-// the row index of the *_rows_* entries: NULL is the identity (n_src is not looked at)
-int check_rows(const int64_t* rows, int64_t n_src)
+// launch(VEC, ROWS), both std::integral_constants, under the panels' access width; ROWS = true with an index,
+// the identity kernels without
+template <typename Launch>
+void by_vec_rows(int vec, bool rows, Launch launch)
 {
-    if (rows && n_src < 0) return srg_fail(SRG_ERR_INVALID, "n_src=%lld panel rows", (long long)n_src);
-    return SRG_OK;
+    auto by_rows = [&](auto V) {
+        if (rows) launch(V, std::true_type{}); else launch(V, std::false_type{});
+    };
+    if (vec == 4) by_rows(std::integral_constant<int, 4>{});
+    else if (vec == 2) by_rows(std::integral_constant<int, 2>{});
+    else by_rows(std::integral_constant<int, 1>{});
+}
+
+// The parameter gradient of either attention once the entry has its shape: k_hop_dzsum over the H vectors at
+// dz, the entry's stage 1, stage 2.  No rows: the sums are empty.  bad: what is wrong with the entry's other
+// arguments (NULL: nothing), reported once there are rows.  stage1(grid, lgCT, s, partials, L) launches the
+// entry's own stage-1 kernel.
+template <typename Stage1>
+int launch_wgrad(const HopShape& hs, const float* dz, int H, int64_t in_dim, float* dw, float* db, void* scratch,
+                 const char* bad, int64_t n, hipStream_t st, Stage1 stage1)
+{
+    if (!dw && !db) return srg_ok();
+    if (hs.empty) {
+        if (dw) SRG_HIP_CHECK(hipMemsetAsync(dw, 0, (size_t)in_dim * sizeof(float), st));
+        if (db) SRG_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float), st));
+        return srg_ok();
+    }
+    if (bad) return srg_fail(SRG_ERR_INVALID, "%s", bad);
+    const WgradLayout L(n, in_dim);
+    int lgCT = 0;
+    while (lgCT < 8 && (1 << lgCT) < hs.cpr) ++lgCT;
+    float* s = static_cast<float*>(scratch);
+    float* partials = s + L.s_floats;
+    const int groups_per_block = 256 >> lgCT;
+    const dim3 grid((unsigned)((L.n_groups + groups_per_block - 1) / groups_per_block),
+                    (unsigned)((hs.cpr + (1 << lgCT) - 1) >> lgCT));
+    hipLaunchKernelGGL(k_hop_dzsum, dim3(hs.thread_blocks), dim3(256), 0, st, dz, s, n, H);
+    stage1(grid, lgCT, s, partials, L);
+    hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials, L, dw,
+                       db);
+    SRG_HIP_CHECK(hipGetLastError());
+    return srg_ok();
 }
 
 }  // namespace
@@ -753,19 +763,17 @@ int srg_hop_scores_rows_f32(const float* const* panels, const int64_t* ldp, cons
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_kind(kind)) return rc;
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    const void* wide[] = {w};
-    const int64_t wide_ld[] = {0};
-    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, wide, wide_ld, 1, hs)) return rc;
-    if (n == 0) return srg_ok();
+    const Operand wide = {w, 0};
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, start, end, n, d, &wide, nullptr, hs)) return rc;
+    if (hs.empty) return srg_ok();
     if (!b || !zflat) return srg_fail(SRG_ERR_INVALID, "null pointer");
     const int H = end - start;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_scores<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, T, start, H, \
-                                        kind, w, b, zflat, n, d, hs.cpr, hs.lgS, rows, n_src)
-    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
-#undef LAUNCH
+    by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+        hipLaunchKernelGGL((k_hop_scores<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, T, start, H, kind, w, b,
+                           zflat, n, d, hs.cpr, hs.lgS, rows, n_src);
+    });
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
@@ -782,23 +790,20 @@ int srg_hop_attend_rows_f32(const float* const* panels, const int64_t* ldp, cons
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_pairing(pairing)) return rc;
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    const void* wide[] = {out};
-    const int64_t wide_ld[] = {ldo};
-    if (ldo < d) return srg_fail(SRG_ERR_INVALID, "ldo=%lld < d=%d", (long long)ldo, d);
-    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, wide, wide_ld, 1, hs)) return rc;
-    if (n == 0) return srg_ok();
+    const Operand wide = {out, ldo};
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, start, end, n, d, &wide, "ldo", hs)) return rc;
+    if (hs.empty) return srg_ok();
     if (!zflat || !P) return srg_fail(SRG_ERR_INVALID, "null pointer");
     const int H = end - start;
     for (int t = start; t < end; ++t)
         if (out == panels[t]) return srg_fail(SRG_ERR_INVALID, "out must not alias a hop panel");
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_hop_softmax, dim3(hs.thread_blocks), dim3(256), 0, st, zflat, pairing, P, n, H);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_combine<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, P, \
-                                        out, ldo, n, hs.cpr, hs.lgS, rows, n_src)
-    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
-#undef LAUNCH
+    by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+        hipLaunchKernelGGL((k_hop_combine<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, P, out, ldo,
+                           n, hs.cpr, hs.lgS, rows, n_src);
+    });
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
@@ -817,21 +822,18 @@ int srg_hop_attend_grad_rows_f32(const float* const* panels, const int64_t* ldp,
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_pairing(pairing)) return rc;
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    const void* wide[] = {G};
-    const int64_t wide_ld[] = {ldg};
-    if (ldg < d) return srg_fail(SRG_ERR_INVALID, "ldg=%lld < d=%d", (long long)ldg, d);
-    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, wide, wide_ld, 1, hs)) return rc;
-    if (n == 0) return srg_ok();
+    const Operand wide = {G, ldg};
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, start, end, n, d, &wide, "ldg", hs)) return rc;
+    if (hs.empty) return srg_ok();
     if (!zflat || !P || !dP || !dzflat) return srg_fail(SRG_ERR_INVALID, "null pointer");
     if (dzflat == zflat || dP == P) return srg_fail(SRG_ERR_INVALID, "dzflat / dP must not alias zflat / P");
     const int H = end - start;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_rowdots<V, false, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, \
-                                        H, G, ldg, dP, n, hs.cpr, hs.lgS, rows, n_src)
-    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
-#undef LAUNCH
+    by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+        hipLaunchKernelGGL((k_hop_rowdots<V, false, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, start, H, G, ldg,
+                           dP, n, hs.cpr, hs.lgS, rows, n_src);
+    });
     hipLaunchKernelGGL(k_hop_jacobian, dim3(hs.thread_blocks), dim3(256), 0, st, zflat, pairing, P, dP, dzflat, n, H);
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
@@ -851,9 +853,7 @@ int srg_hop_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t T, int32_t H
     if (!bytes) return srg_fail(SRG_ERR_INVALID, "null pointer");
     if (n < 0 || d < 1 || T < 1 || T > SRG_HOP_MAX || H < 1 || H > T)
         return srg_fail(SRG_ERR_INVALID, "bad shape n=%lld d=%d T=%d H=%d", (long long)n, d, T, H);
-    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
-    // s [n], then partials [n_groups, in_dim + 1], each row of either rounded up to 16 bytes
-    *bytes = (pad4(n) + n_groups * pad4((int64_t)ref_dim(kind, T, d) + d + 1)) * (int64_t)sizeof(float);
+    *bytes = WgradLayout(n, (int64_t)ref_dim(kind, T, d) + d).bytes();
     return srg_ok();
 }
 
@@ -863,38 +863,19 @@ int srg_hop_scores_grad_rows_f32(const float* const* panels, const int64_t* ldp,
 {
     SRG_DEVICE_GUARD(stream);
     if (int rc = check_kind(kind)) return rc;
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    if (int rc = hop_shape(panels, ldp, T, start, end, n, d, nullptr, nullptr, 0, hs)) return rc;
-    if (!dw && !db) return srg_ok();
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, start, end, n, d, nullptr, nullptr, hs)) return rc;
     const int H = end - start;
-    const int rd = ref_dim(kind, T, d), in_dim = rd + d;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0) {   // empty sums
-        if (dw) SRG_HIP_CHECK(hipMemsetAsync(dw, 0, (size_t)in_dim * sizeof(float), st));
-        if (db) SRG_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float), st));
-        return srg_ok();
-    }
-    if (!dzflat || !scratch || !aligned(scratch, 16))
-        return srg_fail(SRG_ERR_INVALID, "dzflat or scratch null, or scratch not 16-byte aligned");
-    const int vec = hs.vec, cpr = hs.cpr;
-    int lgCT = 0;
-    while (lgCT < 8 && (1 << lgCT) < cpr) ++lgCT;
-    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
-    float* s = static_cast<float*>(scratch);
-    float* partials = s + pad4(n);
-    const int groups_per_block = 256 >> lgCT;
-    const dim3 grid((unsigned)((n_groups + groups_per_block - 1) / groups_per_block),
-                    (unsigned)((cpr + (1 << lgCT) - 1) >> lgCT));
-    hipLaunchKernelGGL(k_hop_dzsum, dim3(hs.thread_blocks), dim3(256), 0, st, dzflat, s, n, H);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_wgrad_partial<V, R>), grid, dim3(256), 0, st, hs.pl, T, start, H, kind, \
-                                        dzflat, s, partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr, rows, n_src)
-    SRG_HOP_BY_VEC(vec, rows, LAUNCH);
-#undef LAUNCH
-    hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials,
-                       n_groups, in_dim, dw, db);
-    SRG_HIP_CHECK(hipGetLastError());
-    return srg_ok();
+    const char* bad = !dzflat || !scratch || !aligned(scratch, 16)
+                          ? "dzflat or scratch null, or scratch not 16-byte aligned" : nullptr;
+    return launch_wgrad(hs, dzflat, H, (int64_t)ref_dim(kind, T, d) + d, dw, db, scratch, bad, n, st,
+                        [&](dim3 grid, int lgCT, const float* s, float* partials, const WgradLayout& L) {
+        by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+            hipLaunchKernelGGL((k_hop_wgrad_partial<V, R>), grid, dim3(256), 0, st, hs.pl, T, start, H, kind, dzflat, s,
+                               partials, n, d, hs.cpr, lgCT, L, dw != nullptr, rows, n_src);
+        });
+    });
 }
 
 int srg_hop_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t start, int32_t end,
@@ -912,18 +893,16 @@ int srg_hop_recur_scores_rows_f32(const float* const* panels, const int64_t* ldp
                                   void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    const void* wide[] = {w};
-    const int64_t wide_ld[] = {0};
-    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, wide, wide_ld, 1, hs)) return rc;
-    if (n == 0) return srg_ok();
+    const Operand wide = {w, 0};
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, 0, end, n, d, &wide, nullptr, hs)) return rc;
+    if (hs.empty) return srg_ok();
     if (!zp || !zq || zp == zq) return srg_fail(SRG_ERR_INVALID, "zp / zq null or the same");
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_recur_scores<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, end, w, \
-                                        zp, zq, n, d, hs.cpr, hs.lgS, rows, n_src)
-    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
-#undef LAUNCH
+    by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+        hipLaunchKernelGGL((k_hop_recur_scores<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, end, w, zp, zq, n,
+                           d, hs.cpr, hs.lgS, rows, n_src);
+    });
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
@@ -939,23 +918,20 @@ int srg_hop_recur_attend_rows_f32(const float* const* panels, const int64_t* ldp
                                   float* work, float* P, float* out, int64_t ldo, int64_t n, int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    const void* wide[] = {out};
-    const int64_t wide_ld[] = {ldo};
-    if (ldo < d) return srg_fail(SRG_ERR_INVALID, "ldo=%lld < d=%d", (long long)ldo, d);
-    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, wide, wide_ld, 1, hs)) return rc;
-    if (n == 0) return srg_ok();
+    const Operand wide = {out, ldo};
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, 0, end, n, d, &wide, "ldo", hs)) return rc;
+    if (hs.empty) return srg_ok();
     if (!zp || !zq || !b || !work || !P) return srg_fail(SRG_ERR_INVALID, "null pointer");
     for (int t = 0; t < end; ++t)
         if (out == panels[t]) return srg_fail(SRG_ERR_INVALID, "out must not alias a hop panel");
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_hop_recur_forward, dim3(recur_blocks(n)), dim3(RECUR_BLOCK),
                        (size_t)RECUR_FWD_VECTORS * end * RECUR_BLOCK * sizeof(float), st, zp, zq, b, work, P, n, end);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_combine<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, P, \
-                                        out, ldo, n, hs.cpr, hs.lgS, rows, n_src)
-    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
-#undef LAUNCH
+    by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+        hipLaunchKernelGGL((k_hop_combine<V, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, P, out, ldo, n,
+                           hs.cpr, hs.lgS, rows, n_src);
+    });
     SRG_HIP_CHECK(hipGetLastError());
     return srg_ok();
 }
@@ -973,20 +949,17 @@ int srg_hop_recur_attend_grad_rows_f32(const float* const* panels, const int64_t
                                        int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    const void* wide[] = {G};
-    const int64_t wide_ld[] = {ldg};
-    if (ldg < d) return srg_fail(SRG_ERR_INVALID, "ldg=%lld < d=%d", (long long)ldg, d);
-    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, wide, wide_ld, 1, hs)) return rc;
-    if (n == 0) return srg_ok();
+    const Operand wide = {G, ldg};
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, 0, end, n, d, &wide, "ldg", hs)) return rc;
+    if (hs.empty) return srg_ok();
     if (!zq || !work || !dzp || !dzq) return srg_fail(SRG_ERR_INVALID, "null pointer");
     if (dzp == dzq || dzp == zq || dzq == zq) return srg_fail(SRG_ERR_INVALID, "dzp, dzq and zq must not alias");
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_rowdots<V, true, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, \
-                                        G, ldg, dzp, n, hs.cpr, hs.lgS, rows, n_src)
-    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
-#undef LAUNCH
+    by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+        hipLaunchKernelGGL((k_hop_rowdots<V, true, R>), dim3(hs.row_blocks), dim3(256), 0, st, hs.pl, 0, end, G, ldg,
+                           dzp, n, hs.cpr, hs.lgS, rows, n_src);
+    });
     hipLaunchKernelGGL(k_hop_recur_backward, dim3(recur_blocks(n)), dim3(RECUR_BLOCK),
                        (size_t)RECUR_BWD_VECTORS * end * RECUR_BLOCK * sizeof(float), st, zq, work, dzp, dzq, n, end);
     SRG_HIP_CHECK(hipGetLastError());
@@ -1005,9 +978,7 @@ int srg_hop_recur_scores_grad_scratch_bytes(int64_t n, int32_t d, int32_t H, int
     if (!bytes) return srg_fail(SRG_ERR_INVALID, "null pointer");
     if (n < 0 || d < 1 || H < 1 || H > SRG_HOP_MAX || 2 * (int64_t)d + 1 > INT32_MAX)
         return srg_fail(SRG_ERR_INVALID, "bad shape n=%lld d=%d H=%d", (long long)n, d, H);
-    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
-    // s [n], then partials [n_groups, 2d + 1], each row of either rounded up to 16 bytes
-    *bytes = (pad4(n) + n_groups * pad4((int64_t)2 * d + 1)) * (int64_t)sizeof(float);
+    *bytes = WgradLayout(n, 2 * (int64_t)d).bytes();
     return srg_ok();
 }
 
@@ -1016,37 +987,18 @@ int srg_hop_recur_scores_grad_rows_f32(const float* const* panels, const int64_t
                                        float* dw, float* db, void* scratch, int64_t n, int32_t d, void* stream)
 {
     SRG_DEVICE_GUARD(stream);
-    if (int rc = check_rows(rows, n_src)) return rc;
     HopShape hs;
-    if (int rc = hop_shape(panels, ldp, T, 0, end, n, d, nullptr, nullptr, 0, hs)) return rc;
-    if (!dw && !db) return srg_ok();
-    const int in_dim = 2 * d;
+    if (int rc = hop_shape(rows, n_src, panels, ldp, T, 0, end, n, d, nullptr, nullptr, hs)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0) {   // empty sums
-        if (dw) SRG_HIP_CHECK(hipMemsetAsync(dw, 0, (size_t)in_dim * sizeof(float), st));
-        if (db) SRG_HIP_CHECK(hipMemsetAsync(db, 0, sizeof(float), st));
-        return srg_ok();
-    }
-    if (!dzp || !dzq || !scratch || !aligned(scratch, 16))
-        return srg_fail(SRG_ERR_INVALID, "dzp, dzq or scratch null, or scratch not 16-byte aligned");
-    const int cpr = hs.cpr;
-    int lgCT = 0;
-    while (lgCT < 8 && (1 << lgCT) < cpr) ++lgCT;
-    const int64_t rpg = rows_per_group(n), n_groups = (n + rpg - 1) / rpg;
-    float* s = static_cast<float*>(scratch);
-    float* partials = s + pad4(n);
-    const int groups_per_block = 256 >> lgCT;
-    const dim3 grid((unsigned)((n_groups + groups_per_block - 1) / groups_per_block),
-                    (unsigned)((cpr + (1 << lgCT) - 1) >> lgCT));
-    hipLaunchKernelGGL(k_hop_dzsum, dim3(hs.thread_blocks), dim3(256), 0, st, dzp, s, n, end);
-#define LAUNCH(V, R) hipLaunchKernelGGL((k_hop_recur_wgrad_partial<V, R>), grid, dim3(256), 0, st, hs.pl, end, dzp, dzq, s, \
-                                        partials, n, d, cpr, lgCT, rpg, n_groups, dw != nullptr, rows, n_src)
-    SRG_HOP_BY_VEC(hs.vec, rows, LAUNCH);
-#undef LAUNCH
-    hipLaunchKernelGGL(k_hop_wgrad_fold, dim3((unsigned)((in_dim + 1 + 255) / 256)), dim3(256), 0, st, partials,
-                       n_groups, in_dim, dw, db);
-    SRG_HIP_CHECK(hipGetLastError());
-    return srg_ok();
+    const char* bad = !dzp || !dzq || !scratch || !aligned(scratch, 16)
+                          ? "dzp, dzq or scratch null, or scratch not 16-byte aligned" : nullptr;
+    return launch_wgrad(hs, dzp, end, 2 * (int64_t)d, dw, db, scratch, bad, n, st,
+                        [&](dim3 grid, int lgCT, const float* s, float* partials, const WgradLayout& L) {
+        by_vec_rows(hs.vec, rows != nullptr, [&](auto V, auto R) {
+            hipLaunchKernelGGL((k_hop_recur_wgrad_partial<V, R>), grid, dim3(256), 0, st, hs.pl, end, dzp, dzq, s,
+                               partials, n, d, hs.cpr, lgCT, L, dw != nullptr, rows, n_src);
+        });
+    });
 }
 
 int srg_hop_recur_scores_grad_f32(const float* const* panels, const int64_t* ldp, int32_t T, int32_t end,

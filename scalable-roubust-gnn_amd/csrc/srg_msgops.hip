@@ -98,14 +98,11 @@ k_hop_simweight(const float* __restrict__ x0, int64_t ldx0, const float* __restr
 {
     typedef typename Vec<float, VEC>::type V;
     constexpr int C = kSimChunks;
-    const int S = 1 << lgS, R = 64 >> lgS;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> lgS, c0 = lane & (S - 1);
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const RowLanes rl(lgS, blockDim.x);
+    const int S = rl.S, c0 = rl.c0;
     // every lane of the wave runs every step (the butterfly reads its partners); rows past the end load nothing
-    for (int64_t base = wave * R; base < n_rows; base += waves * R) {
-        const int64_t r = base + g;
+    for (int64_t base = rl.first; base < n_rows; base += rl.stride) {
+        const int64_t r = base + rl.g;
         const bool live = r < n_rows;
         const float* yr = y + r * ldy;
         const float* xr = hop0 ? yr : x0 + r * ldx0;
@@ -147,10 +144,7 @@ k_hop_simweight(const float* __restrict__ x0, int64_t ldx0, const float* __restr
                 }
             }
         }
-        for (int m = S >> 1; m > 0; m >>= 1) {
-            ny = __fadd_rn(ny, __shfl_xor(ny, m));
-            dot = __fadd_rn(dot, __shfl_xor(dot, m));
-        }
+        butterfly_add(S, ny, dot);
         if (hop0) dot = ny;
         const float norm = __fadd_rn(__fsqrt_rn(ny), 1e-10f);
         const float nr = hop0 ? norm : (live ? n0[r] : 1.0f);
@@ -333,11 +327,8 @@ int srg_hop_simweight_f32(const float* x0, int64_t ldx0, const float* y, int64_t
             (hop0 || rows_aligned(v, sizeof(float), d, {{x0, ldx0}})))
             vec = v;
     const int cpr = d / vec;
-    int lgS = 0;
-    while (lgS < 6 && (1 << lgS) < cpr) ++lgS;
+    const auto [lgS, blocks] = row_lanes_grid(cpr, n_rows);
     const bool hold = cpr <= (kSimChunks << lgS);
-    const int64_t rows_per_block = (int64_t)(256 / 64) * (64 >> lgS);
-    const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + rows_per_block - 1) / rows_per_block, 256 * 64);
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define SRG_SIMWEIGHT(V, H) hipLaunchKernelGGL((k_hop_simweight<V, H>), dim3(blocks), dim3(256), 0, st, x0, ldx0, y, \
                                                ldy, n0, acc, lda, z, e_out, lde, n_rows, cpr, lgS, init, hop0)

@@ -106,15 +106,40 @@ def _check(feat_list, start, end, kind, weight, bias, kinds=KINDS):
     return start, end
 
 
+def _batch(feats, index):
+    """(dev, n_src, d, n): the panels' device, rows and columns, and the rows attended over."""
+    n_src, d = feats[0].shape
+    return feats[0].device, n_src, d, n_src if index is None else index.numel()
+
+
+def _grad_operand(grad, n, d):
+    """(G, ldg): grad as float32 rows of unit column stride, as it is where it already is that."""
+    G = grad if grad.dtype == torch.float32 and grad.stride(1) == 1 and (n <= 1 or grad.stride(0) >= d) \
+        else grad.to(torch.float32).contiguous()
+    return G, G.stride(0) if n > 1 else d
+
+
+def _param_grads(dev, width, wants, query, *shape):
+    """(dw, db, nbytes): the wanted gradients' buffers (None for the other) and the size `query` gives for the
+    parameter gradient's scratch at `shape`."""
+    dw = torch.empty(width, dtype=torch.float32, device=dev) if wants[0] else None
+    db = torch.empty(1, dtype=torch.float32, device=dev) if wants[1] else None
+    nbytes = ctypes.c_int64(0)
+    _lib.check(_lib.query(query, *shape, ctypes.byref(nbytes)), query)
+    return dw, db, nbytes.value
+
+
+def _grads(dw, db, w_shape, b_shape, n_rest):
+    """backward's tuple: the weight's and the bias's gradient, None for each of the n_rest other inputs."""
+    return (None if dw is None else dw.view(w_shape), None if db is None else db.view(b_shape)) + (None,) * n_rest
+
+
 class _HopAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, bias, start, end, kind, index, *feats):
-        dev = feats[0].device
-        n_src, d = feats[0].shape
-        n = n_src if index is None else index.numel()
+        dev, n_src, d, n = _batch(feats, index)
         T, H = len(feats), end - start
-        w = weight.detach().contiguous().view(-1)
-        b = bias.detach().contiguous().view(-1)
+        w, b = weight.detach().contiguous().view(-1), bias.detach().contiguous().view(-1)
         ptrs, lds = _panel_args(feats)
         zflat = torch.empty(H * n, dtype=torch.float32, device=dev)
         P = torch.empty((n, H), dtype=torch.float32, device=dev)
@@ -134,35 +159,27 @@ class _HopAttention(torch.autograd.Function):
     def backward(ctx, grad):
         P, zflat, index, *feats = ctx.saved_tensors
         start, end, kind, w_shape, b_shape = ctx.meta
-        want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        none = (None,) * (4 + len(feats))
-        if not (want_w or want_b):
-            return (None, None) + none
-        dev = feats[0].device
-        n_src, d = feats[0].shape
-        n = n_src if index is None else index.numel()
+        wants = ctx.needs_input_grad[:2]
+        if not any(wants):
+            return _grads(None, None, w_shape, b_shape, 4 + len(feats))
+        dev, n_src, d, n = _batch(feats, index)
         T, H = len(feats), end - start
-        G = grad if grad.dtype == torch.float32 and grad.stride(1) == 1 and (n <= 1 or grad.stride(0) >= d) \
-            else grad.to(torch.float32).contiguous()
-        ldg = G.stride(0) if n > 1 else d
+        G, ldg = _grad_operand(grad, n, d)
         ptrs, lds = _panel_args(feats)
         dP = torch.empty((n, H), dtype=torch.float32, device=dev)
         dz = torch.empty(H * n, dtype=torch.float32, device=dev)
-        dw = torch.empty(in_dim(kind, T, d), dtype=torch.float32, device=dev) if want_w else None
-        db = torch.empty(1, dtype=torch.float32, device=dev) if want_b else None
-        nbytes = ctypes.c_int64(0)
-        _lib.check(_lib.query("srg_hop_scores_grad_scratch_bytes", n, d, T, H, KINDS[kind], ctypes.byref(nbytes)),
-                   "srg_hop_scores_grad_scratch_bytes")
+        dw, db, nbytes = _param_grads(dev, in_dim(kind, T, d), wants, "srg_hop_scores_grad_scratch_bytes", n, d, T, H,
+                                      KINDS[kind])
         with torch.cuda.device(dev):
             st = _lib.stream(dev)
             _call(dev, "srg_hop_attend_grad_f32", ptrs, lds, index, n_src, T, start, end, G.data_ptr(), ldg,
                   zflat.data_ptr(), P.data_ptr(), _pairing(kind), dP.data_ptr(), dz.data_ptr(), n, d, st)
             del dP
-            scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+            scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
             _call(dev, "srg_hop_scores_grad_f32", ptrs, lds, index, n_src, T, start, end, KINDS[kind], dz.data_ptr(),
-                  dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
+                  dw.data_ptr() if wants[0] else None, db.data_ptr() if wants[1] else None, scratch.data_ptr(),
                   n, d, st)
-        return (dw.view(w_shape) if want_w else None, db.view(b_shape) if want_b else None) + none
+        return _grads(dw, db, w_shape, b_shape, 4 + len(feats))
 
 
 def hop_attention(feat_list, start, end, kind, weight, bias, index=None, check=True):
@@ -185,12 +202,9 @@ def hop_attention(feat_list, start, end, kind, weight, bias, index=None, check=T
 class _HopAttentionRecursive(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, bias, end, index, *feats):
-        dev = feats[0].device
-        n_src, d = feats[0].shape
-        n = n_src if index is None else index.numel()
+        dev, n_src, d, n = _batch(feats, index)
         T, H = len(feats), end
-        w = weight.detach().contiguous().view(-1)
-        b = bias.detach().contiguous().view(-1)
+        w, b = weight.detach().contiguous().view(-1), bias.detach().contiguous().view(-1)
         ptrs, lds = _panel_args(feats)
         zp = torch.empty(H * n, dtype=torch.float32, device=dev)
         zq = torch.empty(H * n, dtype=torch.float32, device=dev)
@@ -212,34 +226,25 @@ class _HopAttentionRecursive(torch.autograd.Function):
     def backward(ctx, grad):
         zq, work, index, *feats = ctx.saved_tensors
         end, w_shape, b_shape = ctx.meta
-        want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        none = (None,) * (2 + len(feats))
-        if not (want_w or want_b):
-            return (None, None) + none
-        dev = feats[0].device
-        n_src, d = feats[0].shape
-        n = n_src if index is None else index.numel()
+        wants = ctx.needs_input_grad[:2]
+        if not any(wants):
+            return _grads(None, None, w_shape, b_shape, 2 + len(feats))
+        dev, n_src, d, n = _batch(feats, index)
         T, H = len(feats), end
-        G = grad if grad.dtype == torch.float32 and grad.stride(1) == 1 and (n <= 1 or grad.stride(0) >= d) \
-            else grad.to(torch.float32).contiguous()
-        ldg = G.stride(0) if n > 1 else d
+        G, ldg = _grad_operand(grad, n, d)
         ptrs, lds = _panel_args(feats)
         dzp = torch.empty(H * n, dtype=torch.float32, device=dev)
         dzq = torch.empty(H * n, dtype=torch.float32, device=dev)
-        dw = torch.empty(2 * d, dtype=torch.float32, device=dev) if want_w else None
-        db = torch.empty(1, dtype=torch.float32, device=dev) if want_b else None
-        nbytes = ctypes.c_int64(0)
-        _lib.check(_lib.query("srg_hop_recur_scores_grad_scratch_bytes", n, d, H, ctypes.byref(nbytes)),
-                   "srg_hop_recur_scores_grad_scratch_bytes")
+        dw, db, nbytes = _param_grads(dev, 2 * d, wants, "srg_hop_recur_scores_grad_scratch_bytes", n, d, H)
         with torch.cuda.device(dev):
             st = _lib.stream(dev)
             _call(dev, "srg_hop_recur_attend_grad_f32", ptrs, lds, index, n_src, T, end, G.data_ptr(), ldg,
                   zq.data_ptr(), work.data_ptr(), dzp.data_ptr(), dzq.data_ptr(), n, d, st)
-            scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev)
+            scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
             _call(dev, "srg_hop_recur_scores_grad_f32", ptrs, lds, index, n_src, T, end, dzp.data_ptr(), dzq.data_ptr(),
-                  dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, scratch.data_ptr(),
+                  dw.data_ptr() if wants[0] else None, db.data_ptr() if wants[1] else None, scratch.data_ptr(),
                   n, d, st)
-        return (dw.view(w_shape) if want_w else None, db.view(b_shape) if want_b else None) + none
+        return _grads(dw, db, w_shape, b_shape, 2 + len(feats))
 
 
 def hop_attention_recursive(feat_list, end, weight, bias, index=None, check=True):
