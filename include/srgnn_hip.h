@@ -958,6 +958,57 @@ int srg_gat_attend_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t
                                int32_t H, int32_t C, const float* M, const float* Z, const float* G, int64_t ldg,
                                const float* dS, float* dHf, int64_t ldd, float* da_src, void* stream);
 
+/* ---- graph attention for a batch of rows: the last layer, whose output the loss reads at a batch only ----
+ * The three entries above for the rows of a batch: the same arithmetic in the same orders,
+ * so for finite operands every result has the bits the full entries give with G zero outside the batch.
+ *   rows  int64 [B]         the batch's target ids, unique; NOT trusted: an id outside [0, n_rows) is never an
+ *                           address
+ *   pos   int32 [n_rows]    pos[rows[b]] = b and -1 elsewhere; NOT trusted: a value outside [0, B) is no member
+ *   eptr  int64 [B + 1]     the prefix sum of the batch rows' lengths, eptr[b + 1] - eptr[b] =
+ *                           indptr[rows[b] + 1] - indptr[rows[b]], nnzB = eptr[B]; trusted as indptr is, but
+ *                           no compact position at or past nnzB is read or written
+ * out, M, Z, G, D and da_dst are compact: row b belongs to rows[b].  a_src, a_dst and Hf are the full tables
+ * (a_dst is read at the row's id).  dS is compact [nnzB, H]: entry k of row rows[b] is at eptr[b] + k.
+ * B outside [0, 2^31 - 64) or nnzB < 0: SRG_ERR_INVALID, with the checks of the full entries. */
+
+/* out [B, H*C] (row stride ldo), M [B, H], Z [B, H]: row b is what srg_gat_attend_f32 gives for row rows[b].
+ * An id outside [0, n_rows) gives out = +0, M = Z = 0.  B == 0 is a no-op; nnz == 0, n_src == 0 or
+ * n_rows == 0 launches no kernel and zeroes out, M and Z. */
+int srg_gat_attend_rows_f32(const int64_t* indptr, const int32_t* indices, int64_t nnz, int64_t n_rows, int64_t n_src,
+                            const int64_t* rows, int64_t B, const float* a_src, const float* a_dst, float slope,
+                            const float* Hf, int64_t ldh, int32_t H, int32_t C, float* out, int64_t ldo, float* M,
+                            float* Z, void* stream);
+
+/* The per-edge part of the backward for the batch, with G = dL/dout [B, H*C] (row stride ldg) and out, M, Z as
+ * srg_gat_attend_rows_f32 left them: D [B, H] (scratch of the caller), dS [nnzB, H] and da_dst [B, H] as in
+ * srg_gat_edge_grad_f32, da_dst[b] summed over [eptr[b], eptr[b + 1]).  A row whose id is out of range
+ * writes nothing to dS.  B == 0 is a no-op; nnz == 0, n_src == 0 or n_rows == 0 zeroes da_dst and launches
+ * nothing.  dS may be NULL when nnzB == 0. */
+int srg_gat_edge_grad_rows_f32(const int64_t* indptr, const int32_t* indices, int64_t nnz, int64_t n_rows,
+                               int64_t n_src, const int64_t* rows, int64_t B, const int64_t* eptr, int64_t nnzB,
+                               const float* a_src, const float* a_dst, float slope, const float* Hf, int64_t ldh,
+                               int32_t H, int32_t C, const float* out, int64_t ldo, const float* M, const float* Z,
+                               const float* G, int64_t ldg, float* D, float* dS, float* da_dst, void* stream);
+
+/* The part over the transpose At (and A's own indptr, for an entry's place in its row).  Entry t of row j of
+ * At, with target i = indices_t[t], is a member when i lies in [0, n_rows) and b = pos[i] in [0, B):
+ *   dHf[j,h*C+c] = chain from +0.0f over the member entries of row j in stored order of
+ *                  fmaf(expf(l_t - M[b,h]) / Z[b,h], G[b,h*C+c], .); a member with Z[b,h] == 0 adds nothing
+ *   da_src[j,h]  = the row sum over row j of At, in the order of the section above, of
+ *                  dS[eptr[b] + (perm[t] - indptr[i]), h] for the members whose perm[t] lies in [0, nnz) and
+ *                  whose compact position lies in [eptr[b], eptr[b + 1]) and below nnzB
+ * Every other entry is skipped, not multiplied by zero, and leaves its position out of the row sum; no value
+ * of indices_t, pos or perm is an address before it is range-checked.  A pos that names another member's
+ * position is not detected: that entry is computed with the other row's M, Z and G.  All n_src rows of
+ * dHf [n_src, H*C] (row stride ldd) and da_src [n_src, H] are written; either may be NULL and is then not
+ * computed.  n_src == 0 is a no-op; nnz == 0, n_rows == 0 or B == 0 zeroes the results. */
+int srg_gat_attend_rows_adjoint_f32(const int64_t* indptr_t, const int32_t* indices_t, const int64_t* perm, int64_t nnz,
+                                    int64_t n_rows, int64_t n_src, const int32_t* pos, int64_t B,
+                                    const int64_t* indptr, const int64_t* eptr, int64_t nnzB, const float* a_src,
+                                    const float* a_dst, float slope, int32_t H, int32_t C, const float* M,
+                                    const float* Z, const float* G, int64_t ldg, const float* dS, float* dHf,
+                                    int64_t ldd, float* da_src, void* stream);
+
 /* ---- multi-GPU: communicators and the row-partitioned K-hop propagation ---------------------------
  * SURVEY.md §8(b) item 5, for C / C++ hosts (the Python package drives the same kernels through
  * torch.distributed: srgnn/dist.py).  RCCL is loaded at run time.  Rank r owns rows

@@ -153,6 +153,9 @@ EXPORTED_SYMBOLS = (
     "srg_gat_attend_f32",
     "srg_gat_edge_grad_f32",
     "srg_gat_attend_adjoint_f32",
+    "srg_gat_attend_rows_f32",
+    "srg_gat_edge_grad_rows_f32",
+    "srg_gat_attend_rows_adjoint_f32",
     "srg_hub_join",
     "srg_hub_side_streams",
     "srg_csr_col_splits",
@@ -324,6 +327,15 @@ def _declare(lib):
     lib.srg_gat_attend_adjoint_f32.argtypes = [_p, _p, _p, _i64, _i64, _i64, _p, _p, _f32, _i32, _i32, _p, _p, _p, _i64,
                                                _p, _p, _i64, _p, _p]
     lib.srg_gat_attend_adjoint_f32.restype = ctypes.c_int
+    lib.srg_gat_attend_rows_f32.argtypes = [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _f32, _p, _i64, _i32, _i32, _p,
+                                            _i64, _p, _p, _p]
+    lib.srg_gat_attend_rows_f32.restype = ctypes.c_int
+    lib.srg_gat_edge_grad_rows_f32.argtypes = [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _f32, _p, _i64, _i32,
+                                               _i32, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p]
+    lib.srg_gat_edge_grad_rows_f32.restype = ctypes.c_int
+    lib.srg_gat_attend_rows_adjoint_f32.argtypes = [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _p, _f32,
+                                                    _i32, _i32, _p, _p, _p, _i64, _p, _p, _i64, _p, _p]
+    lib.srg_gat_attend_rows_adjoint_f32.restype = ctypes.c_int
     lib.srg_hub_join.argtypes = [_p]
     lib.srg_hub_join.restype = ctypes.c_int
     lib.srg_hub_side_streams.argtypes = []

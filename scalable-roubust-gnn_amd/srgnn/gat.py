@@ -10,6 +10,11 @@ libsrgnn_hip that keep nothing per edge but an [nnz, H] gradient of the scores i
   ds, da_dst     = srg_gat_edge_grad_f32         the gradient of the scores, over A
   dHf, da_src    = srg_gat_attend_adjoint_f32    the adjoint gather and the source sums, over At and perm
 
+and, for the last layer, whose output the loss reads at a batch of rows only (rows=), the
+same three for those rows: srg_gat_attend_rows_f32, srg_gat_edge_grad_rows_f32 and
+srg_gat_attend_rows_adjoint_f32 keep out, M, Z, D and the gradient of the scores for the batch alone and give,
+on finite operands, the bits of the full path with a cotangent that is zero outside the batch.
+
 GATGraph holds the structure (A over targets, its transpose and the permutation between them), built once;
 gat_attend is the differentiable aggregation (attend_forward and attend_backward are the same calls without
 autograd, supported for callers who keep M and Z themselves); GATConv and GAT are the layer and the model with PyG's
@@ -147,8 +152,45 @@ class GATGraph:
 
 
 # ---- the three entries ------------------------------------------------------------------------------
-def _check(graph, Hf, a_src, a_dst, slope):
-    """(H, C) after gat_attend's argument checks."""
+class _Batch:
+    """A batch of target rows as the rows entries take it: ids int64 [B] (unique), pos int32 [n] with
+    pos[ids[b]] = b and -1 elsewhere, and, built when the backward first asks, eptr int64 [B + 1], the prefix
+    sum of the batch rows' lengths, with nnzB = eptr[B]."""
+
+    def __init__(self, graph, ids, pos):
+        self.graph, self.ids, self.pos = graph, ids, pos
+        self.B = ids.numel()
+        self._eptr = None
+
+    def eptr(self):
+        if self._eptr is None:
+            ip = self.graph.indptr
+            e = torch.zeros(self.B + 1, dtype=torch.int64, device=ip.device)
+            if self.B:
+                torch.cumsum(ip[self.ids + 1] - ip[self.ids], 0, out=e[1:])
+            self._eptr = (e, int(e[-1]))
+        return self._eptr
+
+
+def _batch_of(graph, rows):
+    """(batch, inverse) for `rows` as gat_attend takes them (graph_conv.batch_rows): inverse is None for unique
+    ids, else the batch holds torch.unique(rows) and rows = unique[inverse]."""
+    from .graph_conv import batch_rows
+    if isinstance(rows, _Batch):
+        if rows.graph is not graph:
+            raise ValueError("the batch was made for another graph")
+        return rows, None
+    ids, pos, unique = batch_rows(rows, graph.n, graph.device)
+    if unique:
+        return _Batch(graph, ids, pos), None
+    uniq, inverse = torch.unique(ids, return_inverse=True)
+    ids, pos, _ = batch_rows(uniq, graph.n, graph.device)
+    return _Batch(graph, ids, pos), inverse
+
+
+def _check(graph, Hf, a_src, a_dst, slope, rows=None):
+    """(H, C) after gat_attend's argument checks; with rows, (H, C, batch, inverse): the ids are checked on
+    whatever device the graph lives, before the device itself is."""
     if not isinstance(graph, GATGraph):
         raise TypeError("gat_attend takes a GATGraph")
     for name, t in (("Hf", Hf), ("a_src", a_src), ("a_dst", a_dst)):
@@ -170,16 +212,28 @@ def _check(graph, Hf, a_src, a_dst, slope):
         raise ValueError(f"H*C={W} exceeds {_lib.SRG_GAT_MAX_WIDTH}")
     if not math.isfinite(float(slope)):
         raise ValueError(f"negative_slope={slope} is not finite")
+    batch = _batch_of(graph, rows) if rows is not None else None
     if not graph.device.type == "cuda":
         raise RuntimeError("gat_attend runs on a HIP device: build the GATGraph there (device=) or move it with to()")
     for name, t in (("Hf", Hf), ("a_src", a_src), ("a_dst", a_dst)):
         if t.device != graph.device:
             raise ValueError(f"{name} is on {t.device}, the graph on {graph.device}")
-    return H, W // H
+    return (H, W // H) if batch is None else (H, W // H, *batch)
 
 
-def attend_forward(graph: GATGraph, Hf, a_src, a_dst, negative_slope: float = 0.2):
-    """(out [n, H*C], M [n, H], Z [n, H]) of srg_gat_attend_f32; no autograd."""
+def _unique_batch(batch, inverse, who):
+    if inverse is not None:
+        raise ValueError(f"{who} takes unique row ids; gat_attend computes a repeated id once")
+    return batch
+
+
+def attend_forward(graph: GATGraph, Hf, a_src, a_dst, negative_slope: float = 0.2, rows=None):
+    """(out [n, H*C], M [n, H], Z [n, H]) of srg_gat_attend_f32; no autograd.  With rows (unique ids, as
+    gat_attend takes them): (out [B, H*C], M [B, H], Z [B, H]) of srg_gat_attend_rows_f32, row b for rows[b]."""
+    if rows is not None:
+        H, C, batch, inverse = _check(graph, Hf, a_src, a_dst, negative_slope, rows)
+        return _attend_rows_forward(graph, Hf, a_src, a_dst, negative_slope, H, C,
+                                    _unique_batch(batch, inverse, "attend_forward"))
     H, C = _check(graph, Hf, a_src, a_dst, negative_slope)
     dev, n = graph.device, graph.n
     Hf, ldh = _panel(Hf.detach(), "Hf", dev)
@@ -193,11 +247,67 @@ def attend_forward(graph: GATGraph, Hf, a_src, a_dst, negative_slope: float = 0.
     return out, M, Z
 
 
+def _attend_rows_forward(graph, Hf, a_src, a_dst, slope, H, C, batch):
+    dev, n, B = graph.device, graph.n, batch.B
+    Hf, ldh = _panel(Hf.detach(), "Hf", dev)
+    a_src, a_dst = a_src.detach().contiguous(), a_dst.detach().contiguous()
+    out = torch.empty((B, H * C), dtype=torch.float32, device=dev)
+    M = torch.empty((B, H), dtype=torch.float32, device=dev)
+    Z = torch.empty((B, H), dtype=torch.float32, device=dev)
+    _lib.call(dev, "srg_gat_attend_rows_f32", _ptr(graph.indptr), _ptr(graph.indices), graph.nnz, n, n,
+              _ptr(batch.ids), B, _ptr(a_src), _ptr(a_dst), float(slope), _ptr(Hf), ldh, H, C, _ptr(out), H * C,
+              _ptr(M), _ptr(Z), _lib.stream(dev))
+    return out, M, Z
+
+
+def _attend_rows_backward(graph, Hf, a_src, a_dst, out, M, Z, G, slope, need, H, C, batch):
+    dev, n, nnz, W, B = graph.device, graph.n, graph.nnz, H * C, batch.B
+    need_h, need_s, need_d = (bool(x) for x in need)
+    Hf, ldh = _panel(Hf.detach(), "Hf", dev)
+    G, ldg = _panel(G.detach(), "G", dev)
+    out, ldo = _panel(out.detach(), "out", dev)
+    if tuple(G.shape) != (B, W) or tuple(out.shape) != (B, W):
+        raise ValueError(f"G and out must be [{B}, {W}], got {tuple(G.shape)} and {tuple(out.shape)}")
+    a_src, a_dst, M, Z = (t.detach().contiguous() for t in (a_src, a_dst, M, Z))
+    if tuple(M.shape) != (B, H) or tuple(Z.shape) != (B, H):
+        raise ValueError(f"M and Z must be [{B}, {H}]")
+    slope, s = float(slope), _lib.stream(dev)
+    dS = da_dst = da_src = dHf = None
+    eptr, nnzB = (None, 0)
+    if need_s or need_d:
+        eptr, nnzB = batch.eptr()
+        D = torch.empty((B, H), dtype=torch.float32, device=dev)
+        dS = torch.empty((nnzB, H), dtype=torch.float32, device=dev)
+        compact = torch.empty((B, H), dtype=torch.float32, device=dev)
+        _lib.call(dev, "srg_gat_edge_grad_rows_f32", _ptr(graph.indptr), _ptr(graph.indices), nnz, n, n,
+                  _ptr(batch.ids), B, eptr.data_ptr(), nnzB, _ptr(a_src), _ptr(a_dst), slope, _ptr(Hf), ldh, H, C,
+                  _ptr(out), ldo, _ptr(M), _ptr(Z), _ptr(G), ldg, _ptr(D), _ptr(dS), _ptr(compact), s)
+        del D
+        if need_d:   # the ids are unique: index_copy_ is deterministic
+            da_dst = torch.zeros((n, H), dtype=torch.float32, device=dev).index_copy_(0, batch.ids, compact)
+        del compact
+    if need_h or need_s:
+        if need_h:
+            dHf = torch.empty((n, W), dtype=torch.float32, device=dev)
+        if need_s:
+            da_src = torch.empty((n, H), dtype=torch.float32, device=dev)
+        _lib.call(dev, "srg_gat_attend_rows_adjoint_f32", _ptr(graph.indptr_t), _ptr(graph.indices_t),
+                  _ptr(graph.perm), nnz, n, n, batch.pos.data_ptr() if n else None, B, graph.indptr.data_ptr(),
+                  eptr.data_ptr() if need_s else None, nnzB, _ptr(a_src), _ptr(a_dst), slope, H, C, _ptr(M), _ptr(Z),
+                  _ptr(G), ldg, _ptr(dS) if need_s else None, _ptr(dHf), W, _ptr(da_src), s)
+    return dHf, da_src, da_dst
+
+
 def attend_backward(graph: GATGraph, Hf, a_src, a_dst, out, M, Z, G, negative_slope: float = 0.2,
-                    need=(True, True, True)):
+                    need=(True, True, True), rows=None):
     """(dHf, da_src, da_dst) from what attend_forward returned and G = dL/dout; an entry of `need` that is
     False gives None and skips the work only it needs (srg_gat_edge_grad_f32 when neither score gradient is
-    asked for)."""
+    asked for).  With rows (the ids attend_forward was given): out, M, Z and G are the batch's [B, .] panels;
+    dHf and da_src are [n, .], and da_dst [n, H] holds the batch's rows and +0 elsewhere."""
+    if rows is not None:
+        H, C, batch, inverse = _check(graph, Hf, a_src, a_dst, negative_slope, rows)
+        return _attend_rows_backward(graph, Hf, a_src, a_dst, out, M, Z, G, negative_slope, need, H, C,
+                                     _unique_batch(batch, inverse, "attend_backward"))
     H, C = _check(graph, Hf, a_src, a_dst, negative_slope)
     dev, n, nnz, W = graph.device, graph.n, graph.nnz, H * C
     need_h, need_s, need_d = (bool(x) for x in need)
@@ -248,16 +358,47 @@ class _GatAttend(torch.autograd.Function):
         return None, dHf, da_src, da_dst, None
 
 
+class _GatAttendRows(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, graph, Hf, a_src, a_dst, slope, batch):
+        H, C = a_src.shape[1], Hf.shape[1] // a_src.shape[1]
+        out, M, Z = _attend_rows_forward(graph, Hf, a_src, a_dst, slope, H, C, batch)
+        ctx.graph, ctx.slope, ctx.batch, ctx.hc = graph, slope, batch, (H, C)
+        ctx.save_for_backward(Hf, a_src, a_dst, out, M, Z)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        Hf, a_src, a_dst, out, M, Z = ctx.saved_tensors
+        dHf, da_src, da_dst = _attend_rows_backward(ctx.graph, Hf, a_src, a_dst, out, M, Z, grad, ctx.slope,
+                                                    ctx.needs_input_grad[1:4], *ctx.hc, ctx.batch)
+        return None, dHf, da_src, da_dst, None, None
+
+
 def gat_attend(graph: GATGraph, Hf: torch.Tensor, a_src: torch.Tensor, a_dst: torch.Tensor,
-               negative_slope: float = 0.2) -> torch.Tensor:
+               negative_slope: float = 0.2, rows=None) -> torch.Tensor:
     """out [n, H*C]: per target i and head h the softmax, over i's incoming edges, of
     leaky_relu(a_src[j,h] + a_dst[i,h]) applied to the rows Hf[j, h*C:(h+1)*C] of their sources.
     Hf: [n, H*C] fp32 (a column window of a wider panel passes as it is); a_src, a_dst: [n, H] fp32; all on
     the graph's device.  Differentiable (once) in Hf, a_src and a_dst; the backward runs only the entries
     the gradients autograd asks for need.  A node without incoming edges gets a row of +0 and contributes
-    nothing to any gradient.  Deterministic: no atomics anywhere."""
-    _check(graph, Hf, a_src, a_dst, negative_slope)
-    return _GatAttend.apply(graph, Hf, a_src, a_dst, float(negative_slope))
+    nothing to any gradient.  Deterministic: no atomics anywhere.
+
+    rows (what graph_conv takes, through batch_rows: a tensor, a list or a range, on the host or the device;
+    negative ids wrap; an id out of range raises IndexError before any launch): out [B, H*C] for those target
+    rows only, the bits of gat_attend(...)[rows], and a backward that keeps nothing per edge outside the batch:
+    dHf and da_src [n, .] and da_dst [n, H] (the batch's rows, +0 elsewhere) have, for finite operands, the
+    bits of the full backward under a cotangent that is zero outside the batch.  A repeated id is computed once
+    (torch.unique) and indexed with the inverse: that branch's backward sums the repeats' cotangents through
+    torch's indexing backward and is only as deterministic as that is."""
+    if rows is None:
+        _check(graph, Hf, a_src, a_dst, negative_slope)
+        return _GatAttend.apply(graph, Hf, a_src, a_dst, float(negative_slope))
+    _, _, batch, inverse = _check(graph, Hf, a_src, a_dst, negative_slope, rows)
+    out = _GatAttendRows.apply(graph, Hf, a_src, a_dst, float(negative_slope), batch)
+    return out if inverse is None else out[inverse]
 
 
 # ---- the layer and the model ------------------------------------------------------------------------
@@ -272,7 +413,8 @@ class GATConv(nn.Module):
     [H*C, in], att_src and att_dst [1, H, C], bias [H*C] with concat, [C] without), Glorot for lin and both
     att, zeros for bias.  forward(x, graph): Hf = lin(x); the scores a_src = <Hf_h, att_src_h> and a_dst
     likewise stay dense torch ops; the aggregation is gat_attend; then the heads are concatenated or
-    averaged and the bias added.  Attention dropout needs the per-edge weights this layer never stores:
+    averaged and the bias added.  forward(x, graph, rows): lin and the scores run over all nodes, the
+    aggregation, the head mean and the bias for the batch only (gat_attend's rows=); the result is [B, .].  Attention dropout needs the per-edge weights this layer never stores:
     dropout > 0 raises NotImplementedError in training mode."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
@@ -308,7 +450,10 @@ class GATConv(nn.Module):
     def _aggregate(self, graph, Hf, a_src, a_dst):
         return gat_attend(graph, Hf, a_src, a_dst, self.negative_slope)
 
-    def forward(self, x: torch.Tensor, graph: GATGraph) -> torch.Tensor:
+    def _aggregate_rows(self, graph, Hf, a_src, a_dst, rows):
+        return gat_attend(graph, Hf, a_src, a_dst, self.negative_slope, rows)
+
+    def forward(self, x: torch.Tensor, graph: GATGraph, rows=None) -> torch.Tensor:
         if not isinstance(graph, GATGraph):
             raise TypeError("GATConv.forward takes a GATGraph (GATGraph.from_edge_index / from_scipy / from_torch_sparse)")
         if graph.has_self_loops != self.add_self_loops:
@@ -324,7 +469,10 @@ class GATConv(nn.Module):
         Hv = Hf.view(-1, H, C)
         a_src = torch.einsum("nhc,hc->nh", Hv, self.att_src[0])
         a_dst = torch.einsum("nhc,hc->nh", Hv, self.att_dst[0])
-        out = self._aggregate(graph, Hf, a_src, a_dst)
+        if rows is None:
+            out = self._aggregate(graph, Hf, a_src, a_dst)
+        else:
+            out = self._aggregate_rows(graph, Hf, a_src, a_dst, rows)
         if not self.concat:
             out = out.view(-1, H, C).mean(dim=1)
         if self.bias is not None:
@@ -338,7 +486,8 @@ class GATConv(nn.Module):
 class GAT(nn.Module):
     """The reference runner's GAT baseline on GATGraphs: num_layers GATConv layers, the inner ones with
     num_heads concatenated heads of hidden_channels each followed by ReLU and feature dropout, the last one
-    a single head of out_channels; forward(x, graph) returns log-probabilities."""
+    a single head of out_channels; forward(x, graph) returns log-probabilities, forward(x, graph, rows) those
+    of a batch of rows [B, out] with the last layer restricted to it (the runner's model(x, adj)[train_idx])."""
 
     def __init__(self, in_channels: int, hidden_channels: int, out_channels: int, num_layers: int, dropout: float,
                  num_heads: int):
@@ -354,7 +503,8 @@ class GAT(nn.Module):
         for conv in self.convs:
             conv.reset_parameters()
 
-    def forward(self, x: torch.Tensor, graph: GATGraph) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, graph: GATGraph, rows=None) -> torch.Tensor:
         for conv in list(self.convs)[:-1]:
             x = nn.functional.dropout(torch.relu(conv(x, graph)), p=self.dropout, training=self.training)
-        return self.convs[-1](x, graph).log_softmax(dim=-1)
+        last = self.convs[-1](x, graph) if rows is None else self.convs[-1](x, graph, rows)
+        return last.log_softmax(dim=-1)
