@@ -676,6 +676,28 @@ int srg_csr_mirror(const int64_t* indptr, const int32_t* indices, const int64_t*
 int srg_csr_validate(const int64_t* indptr, const int32_t* indices, int64_t n_rows,
                      int64_t nnz, int64_t n_cols, void* stream);
 
+/* The induced sub-graph of a node set (srgnn.cluster, DESIGN.md 5.12: the Cluster-GCN mini-batches of the
+ * reference's train_minibatch): row b < B of the result is row nodes[b] of the operator (indptr int64 from 0
+ * to nnz, trusted; indices int32, NOT trusted), its entries filtered and relabelled through pos.
+ *   pos given (int32 [n_cols], pos[nodes[b]] = b and -1 elsewhere): an entry with column id c is kept iff
+ *     0 <= c < n_cols and pos[c] >= 0, and stored with column id pos[c]: scipy's A[S][:, S] for S = nodes.
+ *   pos NULL (a row slice): every entry is kept and its id copied verbatim: scipy's A[S].
+ * Kept entries keep the operator's stored order inside their row, duplicates stay duplicates, out_val is
+ * the entry's value bit for bit and out_eid its index in indices / values.  nodes: int64 [B] on the device,
+ * distinct, in any order; a nodes[b] outside [0, n_rows) gives an empty row and is never used as an address,
+ * nor is a column id outside [0, n_cols).
+ * Two passes over the same arguments, as srg_spgemm_f32: phase 0 writes cnt[b] = kept entries of row b
+ * (int64 [B]); the caller forms ptr (int64 [B + 1], the exclusive prefix sum of cnt) and allocates the
+ * outputs of ptr[B] entries; phase 1 writes row b's kept entries at ptr[b] .. of out_idx and, where not
+ * NULL, out_val (needs values) and out_eid.  A kept entry's slot is its rank among its row's kept entries:
+ * no atomics, the same bytes from run to run.  Row lengths, nnz and the output size are 64-bit; n_cols and
+ * B are at most 2^31 - 1 (pos is int32).  B == 0 launches nothing; another phase, a negative size, n_cols
+ * or B >= 2^31: SRG_ERR_INVALID.  Asynchronous on `stream`; neither allocates nor synchronises. */
+int srg_csr_induced_f32(int phase, const int64_t* indptr, const int32_t* indices, const float* values,
+                        int64_t n_rows, int64_t n_cols, const int64_t* nodes, int64_t B, const int32_t* pos,
+                        int64_t* cnt, const int64_t* ptr, int32_t* out_idx, float* out_val, int64_t* out_eid,
+                        void* stream);
+
 /* ---- the sparse wavelet basis built on the device ---------------------------------------------------
  * SpectralModel.calculate_wavelet + normalize_matrices (SSRG/models/base_scalable/base_model.py:236-265,
  * 287-290) from the filter's dense output (srg_cheby_step_f64's R) to the L1-normalised CSR basis, without

@@ -9,6 +9,7 @@ yyysyyy/Scalable-Roubust-GNN.
     wavelet_conv  the wavelet layers' filter phi diag(theta) phi^-1 Z without its n x n product, with autograd
     graph_conv    GCN's sparse products with autograd: the exact hop both ways, row-restricted for the last layer
     gat           the fused GAT layer: GATGraph, gat_attend, GATConv, GAT (forward and backward on the device)
+    cluster       Cluster-GCN mini-batches: induced_subgraph, ClusterData, ClusterLoader (the runner's train_minibatch)
     dist      1-D row partition over torch.distributed (RCCL over xGMI), one process per GPU
     synth     deterministic synthetic graphs / features (counter-based hash, CPU == GPU)
     roofline  byte models of SURVEY.md §8(d)
