@@ -11,7 +11,9 @@
  *      pointing that load_library call at this library moves the product onto the GPU unchanged.
  *
  *  (B) Device entry points (device pointers, asynchronous on the caller's HIP stream) used by the
- *      device-resident K-hop driver and by the row-partitioned multi-GPU path.
+ *      device-resident K-hop driver and by the row-partitioned multi-GPU path, and those of the
+ *      runner's baselines: graph convolution, graph attention, the Cluster-GCN batch extraction
+ *      (srg_csr_induced_f32) and neighbour sampling for GraphSAGE (srg_csr_sample_f32).
  *
  * Conventions for (B):
  *   - Status: 0 on success, a negative SRG_ERR_* code on failure; srg_last_error() (thread-local)
@@ -697,6 +699,34 @@ int srg_csr_induced_f32(int phase, const int64_t* indptr, const int32_t* indices
                         int64_t n_rows, int64_t n_cols, const int64_t* nodes, int64_t B, const int32_t* pos,
                         int64_t* cnt, const int64_t* ptr, int32_t* out_idx, float* out_val, int64_t* out_eid,
                         void* stream);
+
+/* The sampled row slice of a node set (srgnn.neighbor, DESIGN.md 5.13: the neighbour-sampled mini-batches
+ * GraphSAGE is trained on): row b < B of the result is row v = nodes[b] of the operator (indptr int64,
+ * trusted; indices int32, copied verbatim and never used as an address; values float or NULL), of stored
+ * length len, cut to at most `fanout` entries:
+ *   cnt = len       if fanout < 0 or len <= fanout: the row is copied in stored order, values bit for bit,
+ *                   out_eid = indptr[v] + position;
+ *   cnt = fanout    otherwise: the entries at the positions p_t = walk(t), t = 0 .. fanout - 1, of the keyed
+ *                   bijection srg_sample_distinct_i64 documents (below), over m = len with no shift past a
+ *                   query node and key = mix(seed + 0x9E3779B97F4A7C15 * (v + 1)).  The key is the node id,
+ *                   not the batch position: a node's sample is a function of (seed, v, len, fanout) alone,
+ *                   whatever batch it is in.  The positions are distinct by construction and are emitted in
+ *                   ascending position, i.e. in stored order: a sampled row's fma chain is a sub-sequence
+ *                   of the full row's.
+ * The count is closed form, so there is no count phase: the caller forms ptr (int64 [B + 1], the exclusive
+ * prefix sum of cnt) from indptr and allocates ptr[B] entries.  The entry trusts ptr[b + 1] - ptr[b] only
+ * where it equals its own cnt: a row for which it does not is not written.  A nodes[b] outside [0, n_rows)
+ * is an empty row and never an address.  out_val (needs values) and out_eid may be NULL.
+ * The cycle walk is bounded by the domain size 4^h, which no cycle of a permutation exceeds; a row whose walk
+ * hit the bound (a bijection's never does) is left unwritten.
+ * 1 <= fanout <= SRG_SAMPLE_MAX_FANOUT or fanout < 0; fanout == 0, fanout > SRG_SAMPLE_MAX_FANOUT, a negative
+ * size or B >= 2^31: SRG_ERR_INVALID.  A sampled row holds fewer than 2^31 entries (a longer one is not
+ * written).  B == 0 launches nothing.  No atomics: the same bytes from run to run.  Asynchronous on `stream`;
+ * neither allocates nor synchronises. */
+#define SRG_SAMPLE_MAX_FANOUT 64
+int srg_csr_sample_f32(const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows,
+                       const int64_t* nodes, int64_t B, int32_t fanout, uint64_t seed, const int64_t* ptr,
+                       int32_t* out_idx, float* out_val, int64_t* out_eid, void* stream);
 
 /* ---- the sparse wavelet basis built on the device ---------------------------------------------------
  * SpectralModel.calculate_wavelet + normalize_matrices (SSRG/models/base_scalable/base_model.py:236-265,

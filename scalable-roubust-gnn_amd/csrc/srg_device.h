@@ -1,6 +1,6 @@
 // srg_device.h -- device code that more than one kernel family uses: vector loads and stores, the chain
 // link and the epilogue arithmetic, the row-wave gather, the filtered row walk, the rows-by-lanes layout of
-// the streaming reductions, the launch constants; and
+// the streaming reductions, the samplers' keyed bijection (host and device), the launch constants; and
 // the host checks that go with them, the vector-width check among them.  Everything is in the anonymous
 // namespace: each translation unit that includes this header compiles its own copy into its own kernels.
 // Not part of the C-ABI (include/srgnn_hip.h).
@@ -114,6 +114,69 @@ __device__ __forceinline__ T bcast_lane(T v, int q)
         return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), q));
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// the keyed bijection of the samplers (srg_sample_distinct_i64, srg_csr_sample_f32; include/srgnn_hip.h
+// states the arithmetic): uint64 only and wrapping, the same on the host and on the device, so that a host
+// program and a host restatement reproduce every draw bit for bit.
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z)
+{
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+
+// the key of row (or node) r under `seed`
+__host__ __device__ __forceinline__ uint64_t sample_key(uint64_t seed, uint64_t r)
+{
+    return mix64(seed + 0x9E3779B97F4A7C15ull * (r + 1));
+}
+
+constexpr uint64_t kWalkFailed = ~uint64_t(0);   // no draw: never below an m <= 2^62
+
+// A four-round Feistel network over 2h bits, cycle-walked into [0, m): m <= 4^h, h the smallest h >= 1 for it.
+struct FeistelWalk {
+    uint64_t rk[4], mask, m;
+    int h;
+    __host__ __device__ __forceinline__ FeistelWalk(uint64_t key, uint64_t m_) : m(m_)
+    {
+        h = 1;
+        while (h < 31 && (uint64_t(1) << (2 * h)) < m) ++h;   // m <= 2^62 = 4^31
+        mask = (uint64_t(1) << h) - 1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rk[i] = key ^ (0xD6E8FEB86659FD93ull * (uint64_t)(i + 1));
+    }
+    // a bijection of [0, 4^h)
+    __host__ __device__ __forceinline__ uint64_t perm(uint64_t x) const
+    {
+        uint64_t L = x >> h, R = x & mask;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t f = mix64(rk[i] ^ R) & mask;
+            const uint64_t nr = L ^ f;
+            L = R;
+            R = nr;
+        }
+        return (L << h) | R;
+    }
+    // x = perm(t); while x >= m: x = perm(x).  t < m lies on a cycle of the permutation that returns to t, so
+    // the walk lands below m within the cycle's length, at most 4^h applications.  The loop is bounded by
+    // that: were perm not a bijection it still ends, with kWalkFailed, instead of spinning.
+    __host__ __device__ __forceinline__ uint64_t walk(uint64_t t) const
+    {
+        const uint64_t bound = uint64_t(1) << (2 * h);
+        uint64_t x = perm(t);
+        for (uint64_t steps = 1; x >= m; ++steps) {
+            if (steps >= bound) return kWalkFailed;
+            x = perm(x);
+        }
+        return x;
+    }
+};
 
 constexpr int kWavesPerBlock = 4;   // 256-thread workgroups
 constexpr int kBlock = 64 * kWavesPerBlock;

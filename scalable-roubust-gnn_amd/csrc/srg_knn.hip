@@ -188,45 +188,23 @@ k_knn_select(const float* __restrict__ X, int64_t ldx, int64_t n, int d, const i
     }
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
 // One wave per row, a lane per draw: the keyed Feistel bijection of [0, 4^h) walked from t until it
-// lands below m = n - 1 (include/srgnn_hip.h states the arithmetic), then shifted past the query node.
+// lands below m = n - 1 (FeistelWalk, srg_device.h; include/srgnn_hip.h states the arithmetic), then shifted
+// past the query node.  A walk that hit its bound (a bijection's never does) writes -1, an id the selection
+// treats as outside and never reads.
 __global__ void __launch_bounds__(kBlock)
 k_sample_distinct(const int64_t* __restrict__ query, const int64_t* __restrict__ cand_ptr, int64_t n_query,
-                  int64_t n, uint64_t seed, int h, int64_t* __restrict__ cand, int64_t block_base)
+                  int64_t n, uint64_t seed, int64_t* __restrict__ cand, int64_t block_base)
 {
     const int lane = threadIdx.x & 63;
     const int64_t r = (block_base + blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
     if (r >= n_query) return;   // wave-uniform
     const int64_t cp = cand_ptr[r], M = cand_ptr[r + 1] - cp;
-    const uint64_t q = (uint64_t)query[r], m = (uint64_t)(n - 1), mask = (uint64_t(1) << h) - 1;
-    const uint64_t key = mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)r + 1));
-    uint64_t rk[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rk[i] = key ^ (0xD6E8FEB86659FD93ull * (uint64_t)(i + 1));
+    const uint64_t q = (uint64_t)query[r];
+    const FeistelWalk fw(sample_key(seed, (uint64_t)r), (uint64_t)(n - 1));
     for (int64_t t = lane; t < M; t += 64) {
-        uint64_t x = (uint64_t)t;
-        do {
-            uint64_t L = x >> h, R = x & mask;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint64_t f = mix64(rk[i] ^ R) & mask;
-                const uint64_t nr = L ^ f;
-                L = R;
-                R = nr;
-            }
-            x = (L << h) | R;
-        } while (x >= m);
-        cand[cp + t] = (int64_t)(x + (x >= q ? 1 : 0));
+        const uint64_t x = fw.walk((uint64_t)t);
+        cand[cp + t] = x == kWalkFailed ? -1 : (int64_t)(x + (x >= q ? 1 : 0));
     }
 }
 
@@ -357,11 +335,9 @@ int srg_sample_distinct_i64(const int64_t* query, const int64_t* cand_ptr, int64
     if (status[0] & kBadQuery) return srg_fail(SRG_ERR_INVALID, "query id outside [0, %lld)", (long long)n);
     if (status[1] == 0) return srg_ok();
     if (!cand) return srg_fail(SRG_ERR_INVALID, "null cand");
-    int h = 1;
-    while ((uint64_t(1) << (2 * h)) < (uint64_t)(n - 1)) ++h;
     const int64_t blocks = (n_query + kWavesPerBlock - 1) / kWavesPerBlock;
     rc = launch_chunks_capped(blocks, SRG_KNN_LAUNCH_ROWS / kWavesPerBlock, [&](int64_t b0, unsigned nb) {
-        hipLaunchKernelGGL(k_sample_distinct, dim3(nb), dim3(kBlock), 0, s, query, cand_ptr, n_query, n, seed, h, cand, b0);
+        hipLaunchKernelGGL(k_sample_distinct, dim3(nb), dim3(kBlock), 0, s, query, cand_ptr, n_query, n, seed, cand, b0);
         return launch_status();
     });
     return rc ? rc : srg_ok();

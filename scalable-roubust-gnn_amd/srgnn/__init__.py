@@ -10,6 +10,8 @@ yyysyyy/Scalable-Roubust-GNN.
     graph_conv    GCN's sparse products with autograd: the exact hop both ways, row-restricted for the last layer
     gat           the fused GAT layer: GATGraph, gat_attend, GATConv, GAT (forward and backward on the device)
     cluster       Cluster-GCN mini-batches: induced_subgraph, ClusterData, ClusterLoader (the runner's train_minibatch)
+    neighbor      neighbour-sampled mini-batches: sample_neighbors, sample_block, NeighborLoader (the runner's NeighborSampler)
+    sage          GraphSAGE's mean layer on the hop: mean_operator, sage_mean, SAGEConv, SAGE
     dist      1-D row partition over torch.distributed (RCCL over xGMI), one process per GPU
     synth     deterministic synthetic graphs / features (counter-based hash, CPU == GPU)
     roofline  byte models of SURVEY.md §8(d)
