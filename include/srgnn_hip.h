@@ -13,7 +13,8 @@
  *  (B) Device entry points (device pointers, asynchronous on the caller's HIP stream) used by the
  *      device-resident K-hop driver and by the row-partitioned multi-GPU path, and those of the
  *      runner's baselines: graph convolution, graph attention, the Cluster-GCN batch extraction
- *      (srg_csr_induced_f32) and neighbour sampling for GraphSAGE (srg_csr_sample_f32).
+ *      (srg_csr_induced_f32), neighbour sampling for GraphSAGE (srg_csr_sample_f32) and the edge head of
+ *      link classification (srg_pair_gather_add_f32, srg_pair_segment_sum_f32).
  *
  * Conventions for (B):
  *   - Status: 0 on success, a negative SRG_ERR_* code on failure; srg_last_error() (thread-local)
@@ -727,6 +728,38 @@ int srg_csr_induced_f32(int phase, const int64_t* indptr, const int32_t* indices
 int srg_csr_sample_f32(const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows,
                        const int64_t* nodes, int64_t B, int32_t fanout, uint64_t seed, const int64_t* ptr,
                        int32_t* out_idx, float* out_val, int64_t* out_eid, void* stream);
+
+/* ---- the edge head of link classification (srgnn.link) -------------------------------
+ * Every base model of the reference ends its link-classification forward with
+ * linear(cat(f[q[:, 0]], f[q[:, 1]], dim=-1)) (SSRG/models/base_scalable/simple_models.py).  With the weight
+ * split by side, W = [W0 | W1], the dense products run once per distinct endpoint node (P = z [W0; W1]^T,
+ * [U, 2C], through the caller's GEMM) and the two passes over the E query pairs below are C wide; nothing of
+ * shape [E, 2h] exists.  All panels are row-major fp32 with leading dimensions in elements (a column window
+ * of a wider panel is fine); rows are read and written 16 bytes at a time when C % 4 == 0 and every base
+ * pointer and leading dimension allows it, 4 bytes at a time otherwise, with the same bits either way. */
+
+/* out[e, c] = (P[q[e, 0], c] + P[q[e, 1], C + c]) + b[c] for e < E, c < C: this association, two fp32
+ * roundings (one without b: b may be NULL).  P: [U, 2C] (ldp >= 2C); q: int64 [E, 2], contiguous, positions
+ * in [0, U): a position outside that range reads as a row of +0.0f and is never used as an address; out:
+ * [E, C] (ldo >= C).  E == 0 or C == 0 launches nothing.  E, U < 2^31 - 64; a negative size or a leading
+ * dimension below its width: SRG_ERR_INVALID.  Asynchronous on `stream`; neither allocates nor
+ * synchronises. */
+int srg_pair_gather_add_f32(const float* P, int64_t ldp, int64_t U, const int64_t* q, const float* b, int64_t E,
+                            int32_t C, float* out, int64_t ldo, void* stream);
+
+/* The adjoint's segment sums: S[v, side * C + c] = the sum of g[e, c] over the slots (e, side) of node v,
+ * i.e. over the e with q[e, side] == v.  The caller hands the incidence over: inc_ptr (int64 [U + 1],
+ * trusted to ascend; clamped to [0, 2E]) and inc_slot (int64 [2E]; slot = 2 e + side, a node's slots
+ * ascending: a stable sort of the 2E positions by node).  Every element is ONE sequential fp32 chain
+ * ((+0.0f + g[e_1, c]) + g[e_2, c]) + ... over the node's slots of that side in stored order; the slots of
+ * the other side are skipped, never added as + 0.  An empty segment gives +0.0f.  A slot outside [0, 2E) is
+ * skipped and never used as an address.  g: [E, C] (ldg >= C); S: [U, 2C] (lds >= 2C), every element written.
+ * No atomics: the same bits from run to run.  A node's segment is one lane group's serial chain (DESIGN.md
+ * 5.14: a node with very many slots is not split).  U == 0 or C == 0 launches nothing.  E, U < 2^31 - 64; a
+ * negative size or a leading dimension below its width: SRG_ERR_INVALID.  Asynchronous on `stream`; neither
+ * allocates nor synchronises. */
+int srg_pair_segment_sum_f32(const float* g, int64_t ldg, int64_t E, const int64_t* inc_ptr, const int64_t* inc_slot,
+                             int64_t U, int32_t C, float* S, int64_t lds, void* stream);
 
 /* ---- the sparse wavelet basis built on the device ---------------------------------------------------
  * SpectralModel.calculate_wavelet + normalize_matrices (SSRG/models/base_scalable/base_model.py:236-265,

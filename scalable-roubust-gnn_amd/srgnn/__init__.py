@@ -12,6 +12,7 @@ yyysyyy/Scalable-Roubust-GNN.
     cluster       Cluster-GCN mini-batches: induced_subgraph, ClusterData, ClusterLoader (the runner's train_minibatch)
     neighbor      neighbour-sampled mini-batches: sample_neighbors, sample_block, NeighborLoader (the runner's NeighborSampler)
     sage          GraphSAGE's mean layer on the hop: mean_operator, sage_mean, SAGEConv, SAGE
+    link          link classification's edge head without its [E, 2h] buffer: EdgeBatch, pair_linear, edge_head, EdgeBatchLoader
     dist      1-D row partition over torch.distributed (RCCL over xGMI), one process per GPU
     synth     deterministic synthetic graphs / features (counter-based hash, CPU == GPU)
     roofline  byte models of SURVEY.md §8(d)

@@ -164,6 +164,8 @@ EXPORTED_SYMBOLS = (
     "srg_csr_validate",
     "srg_csr_induced_f32",
     "srg_csr_sample_f32",
+    "srg_pair_gather_add_f32",
+    "srg_pair_segment_sum_f32",
     "srg_dense_sparsify_f64",
     "srg_csr_append_rows_f32",
     "srg_csr_row_normalize_l1_f32",
@@ -348,6 +350,10 @@ def _declare(lib):
     lib.srg_csr_induced_f32.restype = ctypes.c_int
     lib.srg_csr_sample_f32.argtypes = [_p, _p, _p, _i64, _p, _i64, _i32, ctypes.c_uint64, _p, _p, _p, _p, _p]
     lib.srg_csr_sample_f32.restype = ctypes.c_int
+    lib.srg_pair_gather_add_f32.argtypes = [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _i64, _p]
+    lib.srg_pair_gather_add_f32.restype = ctypes.c_int
+    lib.srg_pair_segment_sum_f32.argtypes = [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _i64, _p]
+    lib.srg_pair_segment_sum_f32.restype = ctypes.c_int
     lib.srg_dense_sparsify_f64.argtypes = [ctypes.c_int, _p, _i64, _i64, _i32, _f64, _i32, _p, _p, _p, _p, _p]
     lib.srg_dense_sparsify_f64.restype = ctypes.c_int
     lib.srg_csr_append_rows_f32.argtypes = [_p, _p, _p, _i64, _p, _p, _p, _p]

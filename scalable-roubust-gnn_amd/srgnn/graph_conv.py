@@ -310,12 +310,17 @@ class GraphConvolution2(nn.Module):
     Same parameters under the same names as Layer2GraphConvolution (fc1_node_edge, fc2_node, fc2_edge,
     linear), so state dicts interchange; `adj` is a GraphConvOperator and `query_edges` selects the edge head.  forward(feature, rows): with query_edges None and
     rows given, the second product runs for those rows only and the result is what the reference's
-    forward(feature)[rows] returns, bit for bit on the forward; the edge head computes all rows."""
+    forward(feature)[rows] returns, bit for bit on the forward.  With query_edges set the edge head computes all
+    rows and concatenates, as the reference does, unless fused_edge_head is set (False by default): then the second
+    product runs for the batch's distinct endpoints only (rows=batch.n_id) and the head is srgnn.link.pair_linear,
+    with no [E, 2h] buffer; query_edges may then be an srgnn.link.EdgeBatch, so that a static split builds its
+    relabelling and incidence once."""
 
     def __init__(self, feat_dim, hidden_dim, output_dim, dropout=0.5):
         super().__init__()
         self.adj = None
         self.query_edges = None
+        self.fused_edge_head = False
         self.fc1_node_edge = nn.Linear(feat_dim, hidden_dim)
         self.fc2_node = nn.Linear(hidden_dim, output_dim)
         self.fc2_edge = nn.Linear(hidden_dim, hidden_dim)
@@ -333,6 +338,13 @@ class GraphConvolution2(nn.Module):
         h = self.dropout(self.relu(self._conv(self.fc1_node_edge(feature))))
         if self.query_edges is None:
             return self._conv(self.fc2_node(h), rows)
-        z = self._conv(self.fc2_edge(h))
+        from .link import EdgeBatch, pair_linear
         q = self.query_edges
+        if self.fused_edge_head:
+            batch = q if isinstance(q, EdgeBatch) else EdgeBatch(q, self.adj.A.n_rows, self.adj.device)
+            z = self._conv(self.fc2_edge(h), batch.n_id)
+            return pair_linear(z, batch, self.linear.weight, self.linear.bias)
+        if isinstance(q, EdgeBatch):
+            q = q.edges
+        z = self._conv(self.fc2_edge(h))
         return self.linear(torch.cat((z[q[:, 0]], z[q[:, 1]]), dim=-1))
